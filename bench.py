@@ -10,6 +10,16 @@ frames, so every rank does a fixed W x H x F samples per step (weak scaling).
 value = all ranks' samples / max-over-ranks wall time of the K timed steps.
 Inputs (scene buffers, image) are resident in HBM before the timed region.
 
+A plain run does what the headline figure needs and nothing else: set-up, the
+W warm-up steps, the K timed steps, the line.  ``--dump-outputs DIR`` adds the
+read-back of the accumulated image after the last timed step (what a caller of
+rt_render receives through rt_read_image / rt_gather_image), written as
+DIR/image.npy (float32, H x W x 4; the inputs are seeded, so two builds run
+with the same arguments can be compared output for output).  Everything else
+the benchmark measures or checks runs only with ``--full``: the CPU baseline,
+the gather's timing and its bit-exact parity check, nan_pixels, the camera-move
+cost and the fast mode's BVH counters.
+
 Workloads (BASELINE.json configs; --preset, default c3 = the metric's config):
   c2  scene 0 (Book-1 final), 1920x1080, sqrt_spp for 1024 spp
   c3  scene 8 (Book-2 final), 1920x1080, sqrt_spp for 4096 spp   <- headline
@@ -17,7 +27,7 @@ Workloads (BASELINE.json configs; --preset, default c3 = the metric's config):
   c5  scene 8, 3840x2160, sqrt_spp for 8192 spp (the 8-GPU config)
 max_depth 5 (the reference CLI default, Main.java:37) unless --depth.
 
-The rank-0 JSON line carries
+The rank-0 JSON line carries (cpu_baseline and gather_parity with --full only)
   * roofline: the render kernel against the VALU issue ceiling (bound "valu"):
     achieved = SQ_INSTS_VALU per launch (rocprofv3 PMC, committed in
     profiles/valu.json for this config) / the launch time measured here with
@@ -45,6 +55,7 @@ sys.path.insert(0, os.path.join(REPO, "raytracing-book_amd"))
 
 import numpy as np  # noqa: E402
 
+DUMP_LIMIT_BYTES = 64 * 10**6  # --dump-outputs: all files together stay below this
 HBM_PEAK_GBS = 8000.0          # MI355X_MICROARCH.md: HBM3E 8.0 TB/s spec
 SIMDS = 1024                   # 256 CUs x 4 SIMD-32
 CLOCK_HZ = 2.4e9               # max clock
@@ -81,6 +92,13 @@ def parse():
     p.add_argument("--cpu-seconds", type=float, default=60.0)
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--png", default=None)
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="after the timed steps, write the image a caller of the timed path reads back as "
+                        "DIR/image.npy (float32; a fixed seeded sample of its rows, listed in DIR/image_rows.npy, "
+                        "if the image is larger than 64 MB)")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baseline, the gather's timing "
+                        "and parity check, nan_pixels, the camera-move cost, the fast mode's BVH counters")
     p.add_argument("--comm-timeout-ms", type=int, default=60000,
                    help="deadline of the native RCCL gather's rt_comm_init / rt_gather_image (rt_comm_set_timeout)")
     p.add_argument("--gather-deadline", type=float, default=240.0,
@@ -318,6 +336,22 @@ def gather_parity(scene, args, full, world, dev, factors, n_frames):
     return ok, checked
 
 
+# ---------------------------------------------------------------- --dump-outputs
+def dump_outputs(full, path):
+    """The image the timed path's caller reads back after the last timed step, as path/image.npy
+    (float32, rows x W x 4).  An image above DUMP_LIMIT_BYTES (C5) is cut to a fixed, seeded sample
+    of whole rows, their indices in path/image_rows.npy (float64, ascending)."""
+    os.makedirs(path, exist_ok=True)
+    a = np.ascontiguousarray(full, dtype=np.float32)
+    if a.nbytes > DUMP_LIMIT_BYTES:
+        H = a.shape[0]
+        k = (DUMP_LIMIT_BYTES - 8 * H - 4096) // (a.nbytes // H)
+        rows = np.sort(np.random.default_rng(0).choice(H, size=k, replace=False))
+        a = np.ascontiguousarray(a[rows])
+        np.save(os.path.join(path, "image_rows.npy"), rows.astype(np.float64))
+    np.save(os.path.join(path, "image.npy"), a)
+
+
 # ---------------------------------------------------------------- roofline
 def roofline(args, frames_per_launch, samples_per_launch, avg_launch_ms):
     """VALU-issue roofline of render_persistent (see module docstring)."""
@@ -527,11 +561,18 @@ def main():
                                      "anchors); bit-exact against the oracle walking the same SAH tree",
                            "bvh_mode_ran": ctx.last_launch()["bvh_mode"]}
     if world > 1:
-        log(f"rank {rank}: timed region done, {value:.1f} Msamples/s; gathering")
+        log(f"rank {rank}: timed region done, {value:.1f} Msamples/s")
+    if not (args.full or args.dump_outputs or args.png):   # a plain run ends with the timed region
+        if rank == 0:
+            print(json.dumps(out), flush=True)
+        if world > 1:
+            torch.distributed.barrier()
+            torch.distributed.destroy_process_group()
+        return
     guard = LineGuard(out, rank, args.gather_deadline if world > 1 else 0)
-    extra = finish(args, scene, ctx, image, rank, world, dev, factors, F * total_steps)
-    if rank != 0:
-        guard.emit({})
+    extra = finish(args, scene, ctx, image, rank, world, dev, factors, F * total_steps, checks=args.full)
+    if rank != 0 or not args.full:
+        guard.emit(extra)
         if world > 1:
             torch.distributed.barrier()
             torch.distributed.destroy_process_group()
@@ -596,8 +637,9 @@ def camera_move_cost(ctx, scene, factors, reps=5):
                     "unchanged (the collapse re-plan and link upload; bench.py camera_move_cost)"}
 
 
-def finish(args, scene, ctx, image, rank, world, dev, factors, n_frames):
-    """After the timed region: the gather of the accumulated stripes to rank 0 (reported
+def finish(args, scene, ctx, image, rank, world, dev, factors, n_frames, checks=True):
+    """After the timed region (--full, or a run that writes the image: --dump-outputs, --png; the
+    latter without the checks, `checks` False, and their fields): the gather of the accumulated stripes to rank 0 (reported
     separately, not in value) and, on rank 0, its bit-exact check.  The product's path behind
     the C ABI first (rt_comm_init + rt_gather_image: ncclSend to rank 0, de-interleave kernel
     there; what a Java host calls), bounded by --comm-timeout-ms on every rank; the torch
@@ -633,6 +675,10 @@ def finish(args, scene, ctx, image, rank, world, dev, factors, n_frames):
     if args.png:
         import rtamd
         rtamd.save_png(full, args.png)
+    if getattr(args, "dump_outputs", None):
+        dump_outputs(full, args.dump_outputs)
+    if not checks:
+        return {"gather_path": gather_path, "gather_native_error": gather_err}
     nan_px = int(np.isnan(full[..., :3]).any(axis=-1).sum())
     g_ok, g_stripes = None, []
     if world > 1 and not args.fast_bvh:   # other ranks wait in the final barrier meanwhile

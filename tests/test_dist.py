@@ -237,6 +237,28 @@ def _bench_module():
     return bench
 
 
+def test_bench_dump_outputs_is_float32_and_bounded(tmp_path):
+    """--dump-outputs: the image as image.npy in float32; above the size limit a fixed sample of whole
+    rows (the same rows every run, listed in image_rows.npy), all files together within the limit."""
+    bench = _bench_module()
+    rng = np.random.default_rng(3)
+    small = rng.random((9, 7, 4), dtype=np.float32)
+    bench.dump_outputs(small, str(tmp_path / "a"))
+    assert sorted(os.listdir(tmp_path / "a")) == ["image.npy"]
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and np.array_equal(got, small)
+    big = rng.random((64, 50, 4), dtype=np.float32)
+    bench.DUMP_LIMIT_BYTES = 4096 + 8 * 64 + 10 * 800    # room for 10 of the 64 rows
+    for d in ("b", "c"):
+        bench.dump_outputs(big, str(tmp_path / d))
+    rows = np.load(tmp_path / "b" / "image_rows.npy")
+    img = np.load(tmp_path / "b" / "image.npy")
+    assert rows.dtype == np.float64 and len(rows) == 10 and (np.diff(rows) > 0).all()
+    assert img.dtype == np.float32 and np.array_equal(img, big[rows.astype(int)])
+    assert np.array_equal(rows, np.load(tmp_path / "c" / "image_rows.npy"))
+    assert sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b")) <= bench.DUMP_LIMIT_BYTES
+
+
 class _BlockingCtx(_FakeCtx):
     """A context whose rt_gather_image never returns (a peer that never posts its half)."""
 
