@@ -177,6 +177,56 @@ int rt_deinterleave_rows(const float* gathered, int width, int height, int world
 enum { RT_BVH_REFERENCE = 0, RT_BVH_SAH = 1 };
 int rt_set_bvh_mode(rt_ctx* ctx, int mode);
 
+/* ---- Per-pixel sample moments and a noise-target render loop -----------------
+ * With moments on, every launch stages its per-frame colours (a one-frame launch too) and
+ * the fold that applies the running mean also keeps, per pixel, the sum of squared
+ * deviations of the frames' colours from their mean (Welford's update, in f32):
+ *   M2.ch += (c.ch - mean_before.ch) * (c.ch - mean_after.ch)   for ch in x, y, z, and
+ *   M2.w likewise for the channel sum y = (c.x + c.y) + c.z;  frame 1 sets M2 = 0.
+ * The running mean is computed by the same operations as without moments: the image is
+ * unchanged bit for bit, and the render kernels are the same.  M2 / (n - 1) is the sample
+ * variance over the n frames, M2 / (n (n - 1)) the estimated variance of the mean.  Frames
+ * are stratified (each frame takes one cell of the sqrt_spp grid), so the variance between
+ * frames overstates the error of the mean: the estimate is conservative.
+ *
+ * State: the moments cover frames 1 .. n.  rt_render from first_frame 1 restarts them, from
+ * n + 1 extends them; any other first_frame, rt_write_image, rt_bind_device_image and
+ * rt_resize (which reallocates them zero-filled) make them invalid until the next render
+ * from frame 1 or rt_write_moments.  Single-device contexts only (RT_ERR_STATE otherwise);
+ * under rt_set_partition every figure is the rank's own rows'. */
+typedef struct rt_tile_sum   { float m2y, y; uint32_t bad, pixels; } rt_tile_sum;
+typedef struct rt_noise_stats{ double sum_m2y, sum_y; uint64_t pixels, bad; int frames, converged; double noise; } rt_noise_stats;
+
+/* Moments on (1) or off (0, frees the buffer); takes effect at the next rt_render.  Off, the
+ * launch plan, kernels and buffers are exactly those of a context that never had them. */
+int rt_set_moments(rt_ctx* ctx, int on);
+/* M2 as W*local_rows*4 floats in the image's layout; RT_ERR_STATE while invalid. */
+int rt_read_moments(rt_ctx* ctx, float* m2_rgba);
+/* Resume from a checkpoint (pairs with rt_write_image, which comes first): M2 of frames
+ * 1 .. n_frames, n_frames >= 1. */
+int rt_write_moments(rt_ctx* ctx, const float* m2_rgba, int n_frames);
+/* One record per 8x8 tile of the local image, tiles row-major, ceil(W/8) per row: the f32
+ * sums of M2.w and of y = (mean.x + mean.y) + mean.z over the tile's pixels, reduced in a fixed
+ * order (lane ty*8+tx, x += x[lane ^ off] for off = 32, 16, 8, 4, 2, 1), so they depend on image
+ * and moments alone.  A pixel whose y or M2.w is not finite is bad: it adds +0 to both sums and
+ * 1 to `bad`.  out may be NULL to query *n_tiles; RT_ERR_LIMIT if cap is short. */
+int rt_read_tile_sums(rt_ctx* ctx, rt_tile_sum* out, int cap, int* n_tiles);
+/* Host only: the tiles summed in order in double; with P = pixels - bad,
+ *   noise = sqrt(max(0, sum_m2y / (frames (frames - 1))) * P) / sum_y,
+ * the estimated RMS error of the mean relative to the mean y (0 when sum_y and the numerator
+ * are 0, +inf when only sum_y is); frames >= 2, converged = 0. */
+int rt_noise_from_tile_sums(const rt_tile_sum* tiles, int n_tiles, int frames, rt_noise_stats* out);
+/* rt_sync, the tile sums, rt_noise_from_tile_sums over the frames held (at least 2).  Ranks of
+ * a partition add sum_m2y, sum_y, pixels and bad across ranks and apply the formula. */
+int rt_noise(rt_ctx* ctx, rt_noise_stats* out);
+/* Render frames first_frame, first_frame + 1, ... in batches of batch_frames (the last may be
+ * shorter), at most max_frames of them; frame f takes rt_frame_rand_factor(seed, f - 1).  After
+ * every batch rt_noise; stops at the first batch boundary with noise <= target_noise
+ * (last->converged = 1), else after max_frames (0).  *frames_done = frames rendered by this
+ * call.  Not pipelined: frames_done and the image depend on the inputs alone. */
+int rt_render_until(rt_ctx* ctx, int first_frame, int max_frames, int batch_frames, uint64_t seed,
+                    float target_noise, int* frames_done, rt_noise_stats* last);
+
 /* Per-frame u_rand_factor for frame index f (0-based) of a seeded render:
  * top 24 bits of splitmix64(seed, f) / 2^24, in [0,1).  Stands in for the
  * reference's (float)Math.random() per frame (RaytraceExecutor.java:124). */

@@ -93,6 +93,13 @@ int rt_debug_count_node_hits(struct rt_ctx* ctx, int on);
 int rt_debug_read_node_hits(struct rt_ctx* ctx, unsigned int* out, size_t words, size_t* n_out);
 int rt_debug_set_collapse_hits(struct rt_ctx* ctx, const unsigned int* hits, size_t n, unsigned long long walks);
 
+/* The first device's staged per-frame colours of the last launch, as
+ * [n_frames][local_rows][W][4] floats (sparse staging decoded: a clear flag is the zero
+ * colour; the fourth component is whatever the kernel stored, folds ignore it).  out may be
+ * NULL to query *n_frames; RT_ERR_LIMIT if cap_floats is short, RT_ERR_STATE when the last
+ * launch was not staged.  tests/test_gpu_moments.py replays the folds from them. */
+int rt_debug_read_samples(struct rt_ctx* ctx, float* out, size_t cap_floats, int* n_frames);
+
 /* Number of visible HIP devices (0 when none). */
 int rt_debug_device_count(void);
 

@@ -10,6 +10,7 @@ import java.nio.ByteBuffer;
 
 import static java.lang.foreign.ValueLayout.ADDRESS;
 import static java.lang.foreign.ValueLayout.JAVA_BYTE;
+import static java.lang.foreign.ValueLayout.JAVA_DOUBLE;
 import static java.lang.foreign.ValueLayout.JAVA_FLOAT;
 import static java.lang.foreign.ValueLayout.JAVA_INT;
 import static java.lang.foreign.ValueLayout.JAVA_LONG;
@@ -91,6 +92,18 @@ public final class RtAmd implements AutoCloseable {
     private static final MethodHandle COMM_SET_TIMEOUT =
             fn("rt_comm_set_timeout", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT));
     private static final MethodHandle COMM_ABORT = fn("rt_comm_abort", FunctionDescriptor.of(JAVA_INT, ADDRESS));
+    private static final MethodHandle SET_MOMENTS = fn("rt_set_moments", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT));
+    private static final MethodHandle READ_MOMENTS = fn("rt_read_moments", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS));
+    private static final MethodHandle WRITE_MOMENTS =
+            fn("rt_write_moments", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT));
+    private static final MethodHandle WRITE_IMAGE = fn("rt_write_image", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS));
+    private static final MethodHandle READ_TILE_SUMS =
+            fn("rt_read_tile_sums", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS));
+    private static final MethodHandle NOISE_FROM_TILE_SUMS =
+            fn("rt_noise_from_tile_sums", FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT, JAVA_INT, ADDRESS));
+    private static final MethodHandle NOISE = fn("rt_noise", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS));
+    private static final MethodHandle RENDER_UNTIL = fn("rt_render_until",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_LONG, JAVA_FLOAT, ADDRESS, ADDRESS));
 
     private final MemorySegment ctx;
     private int width, height;
@@ -289,6 +302,94 @@ public final class RtAmd implements AutoCloseable {
     /** How the last gather ran: 0 host, 1 peer copies, 2 RCCL; -1 before any. */
     public int gatherPath() {
         return call(() -> (int) GATHER_PATH.invokeExact(ctx));
+    }
+
+    /** rt.h rt_noise_stats: the image-level noise figure of the per-pixel sample moments. */
+    public record NoiseStats(double sumM2y, double sumY, long pixels, long bad, int frames, boolean converged,
+                             double noise) {
+        static final long BYTES = 48;
+
+        static NoiseStats of(MemorySegment s) {
+            return new NoiseStats(s.get(JAVA_DOUBLE, 0), s.get(JAVA_DOUBLE, 8), s.get(JAVA_LONG, 16), s.get(JAVA_LONG, 24),
+                    s.get(JAVA_INT, 32), s.get(JAVA_INT, 36) != 0, s.get(JAVA_DOUBLE, 40));
+        }
+    }
+
+    private int localRows() {
+        return world > 1 ? call(() -> (int) LOCAL_ROWS.invokeExact(height, rank, world, stripeRows)) : height;
+    }
+
+    /** rt_set_moments: keep per-pixel second moments beside the running mean (one device; same image bits). */
+    public void setMoments(boolean on) {
+        check(call(() -> (int) SET_MOMENTS.invokeExact(ctx, on ? 1 : 0)), ctx);
+    }
+
+    /** M2 as width * local rows * 4 floats (x, y, z, channel sum). */
+    public float[] readMoments() {
+        int rows = localRows();
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment m2 = a.allocate(JAVA_FLOAT, (long) width * rows * 4);
+            check(call(() -> (int) READ_MOMENTS.invokeExact(ctx, m2)), ctx);
+            return m2.toArray(JAVA_FLOAT);
+        }
+    }
+
+    /** Resume a checkpoint: the image, then its moments over frames 1 .. nFrames. */
+    public void writeCheckpoint(float[] rgba, float[] m2, int nFrames) {
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment img = a.allocateFrom(JAVA_FLOAT, rgba);
+            check(call(() -> (int) WRITE_IMAGE.invokeExact(ctx, img)), ctx);
+            MemorySegment seg = a.allocateFrom(JAVA_FLOAT, m2);
+            check(call(() -> (int) WRITE_MOMENTS.invokeExact(ctx, seg, nFrames)), ctx);
+        }
+    }
+
+    /** rt_read_tile_sums as raw 16-byte records (float m2y, float y, int bad, int pixels), 4 ints each. */
+    public int[] readTileSums() {
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment n = a.allocate(JAVA_INT);
+            check(call(() -> (int) READ_TILE_SUMS.invokeExact(ctx, MemorySegment.NULL, 0, n)), ctx);
+            int tiles = n.get(JAVA_INT, 0);
+            MemorySegment out = a.allocate(JAVA_INT, (long) tiles * 4);
+            check(call(() -> (int) READ_TILE_SUMS.invokeExact(ctx, out, tiles, n)), ctx);
+            return out.toArray(JAVA_INT);
+        }
+    }
+
+    /** rt_noise_from_tile_sums over such records (several ranks' concatenated, for a partition). */
+    public static NoiseStats noiseFromTileSums(int[] records, int frames) {
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment in = a.allocateFrom(JAVA_INT, records);
+            MemorySegment st = a.allocate(NoiseStats.BYTES);
+            int rc = call(() -> (int) NOISE_FROM_TILE_SUMS.invokeExact(in, records.length / 4, frames, st));
+            if (rc != 0) throw new IllegalArgumentException("rt_noise_from_tile_sums: frames >= 2 required");
+            return NoiseStats.of(st);
+        }
+    }
+
+    /** rt_noise: waits for the queued renders, then the figure over the frames held (at least 2). */
+    public NoiseStats noise() {
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment st = a.allocate(NoiseStats.BYTES);
+            check(call(() -> (int) NOISE.invokeExact(ctx, st)), ctx);
+            return NoiseStats.of(st);
+        }
+    }
+
+    /**
+     * rt_render_until: batches of batchFrames frames from firstFrame until noise &lt;= targetNoise or
+     * maxFrames are rendered; frame f takes rt_frame_rand_factor(seed, f - 1).  framesDone[0] = frames rendered.
+     */
+    public NoiseStats renderUntil(int firstFrame, int maxFrames, int batchFrames, long seed, float targetNoise,
+                                  int[] framesDone) {
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment done = a.allocate(JAVA_INT);
+            MemorySegment st = a.allocate(NoiseStats.BYTES);
+            check(call(() -> (int) RENDER_UNTIL.invokeExact(ctx, firstFrame, maxFrames, batchFrames, seed, targetNoise,
+                    done, st)), ctx);
+            framesDone[0] = done.get(JAVA_INT, 0);
+            return NoiseStats.of(st);
+        }
     }
 
     public int width() {

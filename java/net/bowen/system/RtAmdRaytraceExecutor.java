@@ -118,6 +118,25 @@ public class RtAmdRaytraceExecutor {
         return Math.max(n, 0);
     }
 
+    /**
+     * Frames in batches of {@code batch} until the image's estimated relative noise
+     * (rt_render_until; needs {@code rt.setMoments(true)}) is at most {@code noise}, or
+     * samplePerPixel frames are done.  No reference counterpart: the per-frame factors are
+     * rt_frame_rand_factor(seed, frame - 1), so the frame count depends on the inputs alone.
+     * When the target is met, samplePerPixel becomes the frames used and
+     * {@link #sampleComplete()} runs the listeners.
+     */
+    public RtAmd.NoiseStats raytraceUntil(float noise, int batch, long seed) {
+        int left = samplePerPixel - numSamples;
+        if (left <= 0) throw new IllegalStateException("raytraceUntil: samplePerPixel is the cap and it is reached");
+        if (numSamples == 0) startMillis = System.currentTimeMillis();
+        int[] done = new int[1];
+        RtAmd.NoiseStats st = rt.renderUntil(numSamples + 1, left, batch, seed, noise, done);
+        numSamples += done[0];
+        if (st.converged()) samplePerPixel = numSamples;
+        return st;
+    }
+
     private int launch(int n) {
         if (n <= 0) return 0;
         if (numSamples == 0) startMillis = System.currentTimeMillis();

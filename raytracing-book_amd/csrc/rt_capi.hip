@@ -96,6 +96,8 @@ struct Device {
     DevBuf tile_done;        // ordered chunks: chunks published per 8x8 tile
     DevBuf samples;          // staged chunks: per-frame colours [frames][local pixels]
     DevBuf sflags;           // sparse staging: per staged sample, 1 where its colour was stored
+    DevBuf m2;               // rt_set_moments: per-pixel float4 second moments [local_rows][W] (rt_moments.hip)
+    DevBuf tile_sums;        // ... and their per-tile sums (rt_read_tile_sums)
     DevBuf wbuf;             // pooled units (ordered / one chunk): per resident wave 64 x chunk_frames colours
     DevBuf finfo;            // exact near-first walk tables (variant 61)
     DevBuf f2inner, f2leaves;
@@ -240,6 +242,14 @@ struct rt_ctx {
     size_t sample_budget = (size_t)32 << 30;   // staged colours per launch, at most (and at most half the free memory)
     int last_launch[RT_LI_N] = {0};
     bool launched = false;
+    // Sample moments (rt_set_moments; single-device contexts): every launch is staged and folded by
+    // fold_moments_kernel.  moments_frames = the frames 1 .. n whose moments Device::m2 holds, 0 =
+    // invalid (nothing rendered yet, a first_frame gap, the image overwritten or resized).
+    bool moments = false;
+    int moments_frames = 0;
+    // the first device's staged colours of the last launch (rt_debug_read_samples): frames, sparse flags
+    int staged_frames = 0;
+    bool staged_sparse = false;
     // gathers (rt_read_image of a multi-device context, rt_gather_image): RT_GATHER_*
     int gather_path = -1;
     bool comm_tried = false;     // ncclCommInitAll of a multi-device context attempted
@@ -1407,6 +1417,22 @@ int alloc_image(rt_ctx* c, Device& d) {
     return RT_OK;
 }
 
+// The second-moment buffer of the current image size, zero-filled; the moments become invalid.
+int alloc_moments(rt_ctx* c, Device& d) {
+    HIPCHK(c, hipSetDevice(d.id));
+    HIPCHK(c, hipStreamSynchronize(d.stream));
+    c->moments_frames = 0;
+    dev_free(d.m2);
+    dev_free(d.tile_sums);
+    const size_t bytes = (size_t)d.local_rows * c->width * 16;
+    if (!bytes) return RT_OK;
+    HIPCHK(c, hipMalloc(&d.m2.ptr, bytes));
+    d.m2.bytes = bytes;
+    HIPCHK(c, hipMemsetAsync(d.m2.ptr, 0, bytes, d.stream));
+    HIPCHK(c, hipStreamSynchronize(d.stream));
+    return RT_OK;
+}
+
 int ensure(rt_ctx* c, Device& d, DevBuf& b, size_t n) {
     if (b.bytes >= n) return RT_OK;
     dev_free(b);
@@ -1774,6 +1800,7 @@ int rt_destroy(rt_ctx* c) {
         dev_free(d.tile_done); dev_free(d.samples); dev_free(d.wbuf); dev_free(d.dquads); dev_free(d.dboxes);
         dev_free(d.finfo); dev_free(d.f2inner); dev_free(d.f2leaves); dev_free(d.links); dev_free(d.dboxc);
         dev_free(d.gather); dev_free(d.full); dev_free(d.perlin_pk); dev_free(d.sflags);
+        dev_free(d.m2); dev_free(d.tile_sums); dev_free(d.node_hits);
         if (d.comm && rccl().ok) (void)rccl().CommDestroy(d.comm);
         if (d.ring) (void)hipHostFree(d.ring);
         for (auto& e : d.ring_ev)
@@ -2066,6 +2093,8 @@ int rt_resize(rt_ctx* c, int w, int h) {
         int r = alloc_image(c, d);
         if (r) return r;
     }
+    c->staged_frames = 0;
+    if (c->moments) return alloc_moments(c, c->devs[0]);
     return RT_OK;
 }
 
@@ -2074,6 +2103,7 @@ int rt_bind_device_image(rt_ctx* c, void* ptr, size_t nbytes) {
     if (c->devs.size() != 1) return set_err(c, RT_ERR_STATE, "device image binding needs a 1-device context");
     Device& d = c->devs[0];
     if (c->width <= 0) return set_err(c, RT_ERR_STATE, "rt_resize first");
+    c->moments_frames = 0;   // another image: its moments are not the ones held
     if (!ptr) {
         d.image_ptr = (float*)d.image.ptr;
         d.image_bound = false;
@@ -2413,6 +2443,18 @@ int rt_render(rt_ctx* c, int first_frame, int n_frames, const float* rand_factor
     a.width = c->width;
     a.height = c->height;
     a.stripe_rows = c->stripe_rows;
+    // Sample moments: every launch staged (one frame or one chunk too) and folded by
+    // fold_moments_kernel.  The moments follow frames 1 .. moments_frames: a render from frame 1
+    // restarts them (the fold zeroes them at frame 1), one from moments_frames + 1 extends them,
+    // any other leaves them invalid.
+    const bool mom = c->moments && n_frames > 0 && c->devs[0].local_rows > 0;   // (a rank may own no row)
+    int mom_after = c->moments_frames;
+    if (mom) {
+        if (!c->devs[0].m2.ptr) return set_err(c, RT_ERR_STATE, "sample moments: no buffer (rt_resize)");
+        const bool follows = first_frame == 1 || (c->moments_frames > 0 && first_frame == c->moments_frames + 1);
+        mom_after = follows ? first_frame - 1 + n_frames : 0;
+        c->moments_frames = 0;   // until every launch is queued
+    }
     uint64_t max_ns = 0;
     for (Device& d : c->devs) {
         HIPCHK(c, hipSetDevice(d.id));
@@ -2476,7 +2518,7 @@ int rt_render(rt_ctx* c, int first_frame, int n_frames, const float* rand_factor
             const long long target = few_tiles ? c->staged_chunk_target : c->chunk_target;
             chunks_wanted = (int)std::min<long long>(RT_MAX_FRAMES_PER_LAUNCH, (target * waves + n_tiles - 1) / n_tiles);
         }
-        const bool staged = chunks_wanted > 1 && few_tiles;
+        const bool staged = mom || (chunks_wanted > 1 && few_tiles);
         const size_t n_pixels = (size_t)d.local_rows * c->width;
         if (staged) {
             // staged colours per launch: at most sample_budget and half the device's free memory
@@ -2520,7 +2562,7 @@ int rt_render(rt_ctx* c, int first_frame, int n_frames, const float* rand_factor
             a.n_chunks = std::max(1, std::min(chunks_wanted, nf));
             a.chunk_frames = (nf + a.n_chunks - 1) / a.n_chunks;
             a.n_chunks = (nf + a.chunk_frames - 1) / a.chunk_frames;
-            if (a.n_chunks == 1) a.samples = nullptr;   // one chunk: the running mean in place
+            if (a.n_chunks == 1 && !mom) a.samples = nullptr;   // one chunk: the running mean in place
             else if (staged) a.samples = (float4*)d.samples.ptr;
             // staged: the last frames as one-frame chunks (the units claimed last are then short,
             // so the grid's waves finish close together); the chunks before keep their size
@@ -2565,11 +2607,13 @@ int rt_render(rt_ctx* c, int first_frame, int n_frames, const float* rand_factor
             HIPCHK(c, hipEventSynchronize(d.ring_ev[slot]));   // the copy that last used this slot is done
             d.ring[slot] = a;
             if (rt_launch_render(d.ring[slot], (rt_kernel_args*)d.args.ptr, d.stream,
-                                 &d == &c->devs[0] ? c->last_launch : nullptr))
+                                 &d == &c->devs[0] ? c->last_launch : nullptr, mom ? d.m2.ptr : nullptr))
                 return set_err(c, RT_ERR_DEVICE, std::string("kernel launch failed: ") +
                                                      hipGetErrorString(hipGetLastError()));
             HIPCHK(c, hipEventRecord(d.ring_ev[slot], d.stream));
             if (&d == &c->devs[0]) {
+                c->staged_frames = a.samples ? nf : 0;
+                c->staged_sparse = a.samples && a.sflags;
                 c->last_launch[RT_LI_BVH_MODE] = c->bvh_mode;
                 c->last_launch[RT_LI_VNODES] = a.box_vnodes ? c->n_vnodes : 0;
                 c->last_launch[RT_LI_COLLAPSED] = c->walk_c ? c->n_dropped : 0;
@@ -2581,6 +2625,7 @@ int rt_render(rt_ctx* c, int first_frame, int n_frames, const float* rand_factor
         c->launched = c->launched || n_frames > 0;
     }
     (void)max_ns;
+    if (mom) c->moments_frames = mom_after;
     return RT_OK;
 }
 
@@ -2672,6 +2717,7 @@ int rt_write_image(rt_ctx* c, const float* rgba) {
     if (c->width <= 0) return set_err(c, RT_ERR_STATE, "no image");
     int r = rt_sync(c);
     if (r) return r;
+    c->moments_frames = 0;   // rt_write_moments restores them from the same checkpoint
     for (Device& d : c->devs) {
         HIPCHK(c, hipSetDevice(d.id));
         std::vector<float> local((size_t)d.local_rows * c->width * 4);
@@ -2689,6 +2735,172 @@ int rt_write_image(rt_ctx* c, const float* rgba) {
         int r2 = h2d(c, d, d.image_ptr, local.data(), local.size() * 4);
         if (r2) return r2;
     }
+    return RT_OK;
+}
+
+// ---- sample moments and the noise-target loop (rt.h; kernels in rt_moments.hip) ----
+
+int rt_set_moments(rt_ctx* c, int on) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if (c->devs.size() != 1) return set_err(c, RT_ERR_STATE, "sample moments need a 1-device context");
+    Device& d = c->devs[0];
+    if (!on) {
+        HIPCHK(c, hipSetDevice(d.id));
+        HIPCHK(c, hipStreamSynchronize(d.stream));
+        dev_free(d.m2);
+        dev_free(d.tile_sums);
+        c->moments = false;
+        c->moments_frames = 0;
+        return RT_OK;
+    }
+    if (c->moments) return RT_OK;
+    c->moments = true;
+    c->moments_frames = 0;
+    return c->width > 0 ? alloc_moments(c, d) : RT_OK;
+}
+
+namespace {
+int moments_ready(rt_ctx* c, bool need_valid) {
+    if (!c->moments) return set_err(c, RT_ERR_STATE, "rt_set_moments(ctx, 1) first");
+    if (c->width <= 0 || !c->devs[0].m2.ptr) return set_err(c, RT_ERR_STATE, "no image");
+    if (need_valid && c->moments_frames < 1)
+        return set_err(c, RT_ERR_STATE, "the moments are invalid: render from frame 1 (or rt_write_moments)");
+    return RT_OK;
+}
+}  // namespace
+
+int rt_read_moments(rt_ctx* c, float* m2_rgba) {
+    if (!c || !m2_rgba) return RT_ERR_INVALID_ARG;
+    int r = moments_ready(c, true);
+    if (!r) r = rt_sync(c);
+    if (r) return r;
+    Device& d = c->devs[0];
+    HIPCHK(c, hipSetDevice(d.id));
+    return d2h(c, d, m2_rgba, d.m2.ptr, (size_t)d.local_rows * c->width * 16);
+}
+
+int rt_write_moments(rt_ctx* c, const float* m2_rgba, int n_frames) {
+    if (!c || !m2_rgba || n_frames < 1) return RT_ERR_INVALID_ARG;
+    int r = moments_ready(c, false);
+    if (!r) r = rt_sync(c);
+    if (r) return r;
+    Device& d = c->devs[0];
+    HIPCHK(c, hipSetDevice(d.id));
+    c->moments_frames = 0;
+    r = h2d(c, d, d.m2.ptr, m2_rgba, (size_t)d.local_rows * c->width * 16);
+    if (r) return r;
+    c->moments_frames = n_frames;
+    return RT_OK;
+}
+
+int rt_read_tile_sums(rt_ctx* c, rt_tile_sum* out, int cap, int* n_tiles) {
+    if (!c || !n_tiles) return RT_ERR_INVALID_ARG;
+    int r = moments_ready(c, false);
+    if (r) return r;
+    Device& d = c->devs[0];
+    const int n = ((c->width + 7) / 8) * ((d.local_rows + 7) / 8);
+    *n_tiles = n;
+    if (!out) return RT_OK;
+    if (cap < n) return set_err(c, RT_ERR_LIMIT, "rt_read_tile_sums: out is too small");
+    r = moments_ready(c, true);
+    if (!r) r = rt_sync(c);
+    if (r || n == 0) return r;
+    HIPCHK(c, hipSetDevice(d.id));
+    r = ensure(c, d, d.tile_sums, (size_t)n * sizeof(rt_tile_sum));
+    if (r) return r;
+    if (rt_launch_tile_sums(d.image_ptr, d.m2.ptr, c->width, d.local_rows, d.tile_sums.ptr, d.stream))
+        return set_err(c, RT_ERR_DEVICE, std::string("tile sums launch failed: ") + hipGetErrorString(hipGetLastError()));
+    return d2h(c, d, out, d.tile_sums.ptr, (size_t)n * sizeof(rt_tile_sum));
+}
+
+int rt_noise_from_tile_sums(const rt_tile_sum* tiles, int n_tiles, int frames, rt_noise_stats* out) {
+    if (!out || n_tiles < 0 || (n_tiles > 0 && !tiles) || frames < 2) return RT_ERR_INVALID_ARG;
+    rt_noise_stats s;
+    std::memset(&s, 0, sizeof(s));
+    for (int i = 0; i < n_tiles; i++) {   // in tile order, in double: the figure depends on the tiles alone
+        s.sum_m2y += (double)tiles[i].m2y;
+        s.sum_y += (double)tiles[i].y;
+        s.pixels += tiles[i].pixels;
+        s.bad += tiles[i].bad;
+    }
+    s.frames = frames;
+    const double p = (double)(s.pixels - s.bad);
+    const double num = std::sqrt(std::max(0.0, s.sum_m2y / ((double)frames * ((double)frames - 1.0))) * p);
+    if (s.sum_y == 0.0) s.noise = num == 0.0 ? 0.0 : (double)INFINITY;
+    else s.noise = num / s.sum_y;
+    *out = s;
+    return RT_OK;
+}
+
+int rt_noise(rt_ctx* c, rt_noise_stats* out) {
+    if (!c || !out) return RT_ERR_INVALID_ARG;
+    int r = moments_ready(c, true);
+    if (r) return r;
+    if (c->moments_frames < 2) return set_err(c, RT_ERR_STATE, "rt_noise needs at least two frames");
+    int n = 0;
+    r = rt_read_tile_sums(c, nullptr, 0, &n);
+    if (r) return r;
+    std::vector<rt_tile_sum> tiles((size_t)n);
+    r = rt_read_tile_sums(c, tiles.data(), n, &n);
+    if (r) return r;
+    return rt_noise_from_tile_sums(tiles.data(), n, c->moments_frames, out);
+}
+
+int rt_render_until(rt_ctx* c, int first_frame, int max_frames, int batch_frames, uint64_t seed, float target_noise,
+                    int* frames_done, rt_noise_stats* last) {
+    if (!c || !frames_done || !last) return RT_ERR_INVALID_ARG;
+    *frames_done = 0;
+    std::memset(last, 0, sizeof(*last));
+    if (first_frame < 1 || max_frames < 1 || batch_frames < 1 || first_frame > INT_MAX - max_frames)
+        return set_err(c, RT_ERR_INVALID_ARG, "first_frame >= 1, max_frames >= 1, batch_frames >= 1");
+    if (!c->moments) return set_err(c, RT_ERR_STATE, "rt_set_moments(ctx, 1) first");
+    std::vector<float> rf((size_t)std::min(batch_frames, max_frames));
+    int done = 0;
+    while (done < max_frames) {
+        const int n = std::min(batch_frames, max_frames - done);
+        for (int i = 0; i < n; i++) rf[i] = rt_frame_rand_factor(seed, (uint64_t)(first_frame + done + i - 1));
+        int r = rt_render(c, first_frame + done, n, rf.data());
+        if (r) return r;
+        done += n;
+        *frames_done = done;
+        if (first_frame + done - 1 < 2) {   // one frame: no variance yet
+            r = rt_sync(c);
+            if (r) return r;
+            last->frames = 1;
+            last->noise = (double)INFINITY;
+            continue;
+        }
+        r = rt_noise(c, last);   // waits for the batch: not pipelined, so the stop depends on the inputs alone
+        if (r) return r;
+        if (last->noise <= (double)target_noise) {
+            last->converged = 1;
+            break;
+        }
+    }
+    return RT_OK;
+}
+
+int rt_debug_read_samples(rt_ctx* c, float* out, size_t cap_floats, int* n_frames) {
+    if (!c || !n_frames) return RT_ERR_INVALID_ARG;
+    if (!c->launched || c->staged_frames <= 0) return set_err(c, RT_ERR_STATE, "the last launch was not staged");
+    Device& d = c->devs[0];
+    const size_t n_pixels = (size_t)d.local_rows * c->width;
+    const int nf = c->staged_frames;
+    *n_frames = nf;
+    if (!out) return RT_OK;
+    if (cap_floats < (size_t)nf * n_pixels * 4) return set_err(c, RT_ERR_LIMIT, "rt_debug_read_samples: out is too small");
+    int r = rt_sync(c);
+    if (r) return r;
+    HIPCHK(c, hipSetDevice(d.id));
+    if (d.samples.bytes < (size_t)nf * n_pixels * 16 || (c->staged_sparse && d.sflags.bytes < (size_t)nf * n_pixels))
+        return set_err(c, RT_ERR_STATE, "the staged colours are gone");
+    r = d2h(c, d, out, d.samples.ptr, (size_t)nf * n_pixels * 16);
+    if (r || !c->staged_sparse) return r;
+    std::vector<uint8_t> fl((size_t)nf * n_pixels);   // a clear flag is the zero colour, never stored
+    r = d2h(c, d, fl.data(), d.sflags.ptr, fl.size());
+    if (r) return r;
+    for (size_t i = 0; i < fl.size(); i++)
+        if (!fl[i]) std::memset(out + i * 4, 0, 16);
     return RT_OK;
 }
 

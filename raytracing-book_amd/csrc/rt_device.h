@@ -19,6 +19,8 @@
 //   samples  : float4 [frames][local_rows*W] per-frame colours (staged-chunk launches; sparse: only
 //              the colours that are not exactly zero are written)
 //   sflags   : uint8 [frames][local_rows*W] sparse staging: 1 where the colour was written
+//   m2       : float4 [local_rows][W] per-pixel second moments of the frames' colours (x, y, z and their
+//              sum), beside the image when rt_set_moments is on (rt_moments.hip); tile_sums: rt_tile_sum [tiles]
 //   wbuf     : float4 [resident waves][2][chunk_frames][64] per-wave sample colours of the
 //              units in flight (pooled units, ordered / one-chunk launches)
 #pragma once
@@ -220,8 +222,14 @@ int rt_launch_render_ab(int shape, rt_kernel_args& a, const rt_kernel_args* d, s
 #endif
 // launcher implemented in rt_kernel.hip
 int rt_resident_waves(void);   // waves a render launch keeps resident on the current device (its grid, at most)
-// sets a.acc_lds; info (may be NULL): RT_LI_* of the launch
-int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int* info);
+// sets a.acc_lds; info (may be NULL): RT_LI_* of the launch; moments (may be NULL): the per-pixel
+// float4 second moments a staged launch's fold also updates (fold_moments_kernel for fold_kernel)
+int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int* info, void* moments = nullptr);
+// launchers implemented in rt_moments.hip
+// a staged launch's colours (a.samples, a.sflags) folded into a.image and moments [n_pixels] float4
+int rt_launch_fold_moments(const rt_kernel_args& a, void* moments, void* stream);
+// image, moments [local_rows][width] float4 -> out: one rt_tile_sum per 8x8 tile, row-major
+int rt_launch_tile_sums(const void* image, const void* moments, int width, int local_rows, void* out, void* stream);
 // Row y of the image in the gathered stripe blocks [world][padded_rows][W]: rank k = s % world
 // of its stripe s = y / stripe_rows, local row (s / world) * stripe_rows + y % stripe_rows
 // (rt_set_partition).  Shared by deinterleave_kernel and rt_debug_deinterleave.

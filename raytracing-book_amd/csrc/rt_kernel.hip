@@ -566,7 +566,7 @@ int rt_resident_waves(void) {
     return cus * 2 * (512 / 64);   // every shape: at most 2 workgroups of 512 per CU (launch_persistent)
 }
 
-int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int* info) {
+int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int* info, void* moments) {
     if (a.local_rows <= 0 || a.width <= 0 || a.n_frames <= 0) return 0;
     hipStream_t st = (hipStream_t)stream;
     // The release library has one kernel structure (tests/test_gpu_*.py pin it to the oracle):
@@ -701,7 +701,9 @@ int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int
 #undef RT_LINK4
 #undef RT_LINK4S
     if (rc) return rc;
-    if (a.samples) {   // staged chunks: the running mean over the launch's frames
+    if (a.samples && moments) {   // ... and the second moments (rt_moments.hip), the same mean
+        if (rt_launch_fold_moments(a, moments, stream)) return -1;
+    } else if (a.samples) {   // staged chunks: the running mean over the launch's frames
         const unsigned blocks = (unsigned)((a.n_pixels + 255) / 256);
         hipLaunchKernelGGL(fold_kernel, dim3(blocks), dim3(256), 0, st, d);
     }

@@ -26,6 +26,10 @@
 // Texture.saveAsPNG) and prints GuiRenderer.draw's status lines
 // (GuiRenderer.java:48-62): "Last raytrace took: <ms> ms." and
 // "Sample: <n>/<spp>." (+ "Render completed in: ..." once complete).
+//
+// Noise target: --noise <x> renders batches of --frames-per-launch frames until the image's
+// estimated relative noise (rt_render_until: per-pixel sample moments, rt.h) is at most x, with
+// -spp as the cap, and prints "Noise target: <frames> frames, noise <value> (...)".  One device.
 #include "rt/rt.h"
 #include "rt/rt_scene.h"
 
@@ -51,7 +55,7 @@ struct Opt {
 };
 
 // commons-cli Options in Main.getOptions order (Main.java:43-70)
-enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_N };
+enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_N };
 const Opt kOpts[O_N] = {
     {"h", "help", false, "print help message"},
     {"s", "scene", true, "scene ID"},
@@ -65,6 +69,7 @@ const Opt kOpts[O_N] = {
     {nullptr, "frames-per-launch", true, "frames per kernel launch (default 64)"},
     {nullptr, "preview", true, "progressive preview PNG, rewritten every --preview-every frames"},
     {nullptr, "preview-every", true, "frames between preview updates (default: --frames-per-launch)"},
+    {nullptr, "noise", true, "stop once the estimated relative noise is at most this (-spp is the cap)"},
 };
 
 // HelpFormatter.printHelp("OpenGL Ray Tracer", options): options sorted by key.
@@ -216,6 +221,16 @@ int main(int argc, char** argv) {
     const std::string preview = get(O_PREVIEW, nullptr);
     const int preview_every = seen[O_PREVIEW_EVERY] ? parse_int(val[O_PREVIEW_EVERY]) : per_launch;
     if (preview_every <= 0) die("rtrender", "--preview-every must be positive");
+    float noise_target = -1.0f;
+    if (seen[O_NOISE]) {
+        char* end = nullptr;
+        noise_target = std::strtof(val[O_NOISE].c_str(), &end);
+        if (val[O_NOISE].empty() || *end != '\0' || !(noise_target >= 0.0f))
+            die("rtrender", "--noise must be a number >= 0");
+        if (devices.size() > 1) die("rtrender", "--noise renders on one device (--devices names more)");
+        if (!preview.empty()) die("rtrender", "--noise and --preview do not combine");
+        if (spp <= 0) die("rtrender", "--noise needs -spp >= 1 (the cap)");
+    }
 
     rts_scene* scene = nullptr;
     if (rts_build(scene_id, width, height, (uint64_t)seed, nullptr, &scene) != 0) die("rts_build", rts_last_error());
@@ -254,7 +269,16 @@ int main(int argc, char** argv) {
     std::vector<float> rf((size_t)per_launch);
     uint64_t device_ns = 0;
     std::vector<float> rgba;
-    for (int f0 = 0; f0 < spp;) {
+    if (seen[O_NOISE]) {
+        rt_noise_stats st;
+        int frames = 0;
+        chk(rt_set_moments(ctx, 1), "rt_set_moments");
+        chk(rt_render_until(ctx, 1, spp, per_launch, (uint64_t)seed, noise_target, &frames, &st), "rt_render_until");
+        std::printf("Noise target: %d frames, noise %.6g (%s)\n", frames, st.noise,
+                    st.converged ? "converged" : "sample cap reached");
+        spp = frames;
+    }
+    for (int f0 = seen[O_NOISE] ? spp : 0; f0 < spp;) {
         int n = std::min(per_launch, spp - f0);
         if (!preview.empty()) n = std::min(n, preview_every - f0 % preview_every);   // stop at the next preview
         for (int i = 0; i < n; i++) rf[i] = rt_frame_rand_factor((uint64_t)seed, (uint64_t)(f0 + i));

@@ -64,8 +64,33 @@ class RtsCamera(ctypes.Structure):
                 ("background", ctypes.c_float * 3)]
 
 
-def _amd_protos(L):
+class RtTileSum(ctypes.Structure):
+    """rt.h rt_tile_sum (numpy: TILE_SUM_DTYPE)."""
+    _fields_ = [("m2y", ctypes.c_float), ("y", ctypes.c_float), ("bad", ctypes.c_uint32), ("pixels", ctypes.c_uint32)]
+
+
+class RtNoiseStats(ctypes.Structure):
+    """rt.h rt_noise_stats."""
+    _fields_ = [("sum_m2y", ctypes.c_double), ("sum_y", ctypes.c_double), ("pixels", ctypes.c_uint64),
+                ("bad", ctypes.c_uint64), ("frames", ctypes.c_int), ("converged", ctypes.c_int),
+                ("noise", ctypes.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+def _amd_protos(L, old_rev=False):
     vp, sz, i, f, u64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_float, ctypes.c_uint64
+    ts_p, ns_p = ctypes.POINTER(RtTileSum), ctypes.POINTER(RtNoiseStats)
+    if not old_rev or hasattr(L, "rt_set_moments"):   # amd_at: a revision from before the sample moments
+        _proto(L, "rt_set_moments", i, vp, i)
+        _proto(L, "rt_read_moments", i, vp, c_float_p)
+        _proto(L, "rt_write_moments", i, vp, c_float_p, i)
+        _proto(L, "rt_read_tile_sums", i, vp, ts_p, i, c_int_p)
+        _proto(L, "rt_noise_from_tile_sums", i, ts_p, i, i, ns_p)
+        _proto(L, "rt_noise", i, vp, ns_p)
+        _proto(L, "rt_render_until", i, vp, i, i, i, u64, f, c_int_p, ns_p)
+        _proto(L, "rt_debug_read_samples", i, vp, c_float_p, sz, c_int_p)
     _proto(L, "rt_abi_version", i)
     _proto(L, "rt_create", i, i, c_int_p, ctypes.POINTER(vp))
     _proto(L, "rt_destroy", i, vp)
@@ -170,7 +195,7 @@ def amd_at(path):
         if not os.path.exists(path):
             raise ImportError(f"{path} is missing")
         _import_torch_first()
-        _amd_at[path] = _amd_protos(ctypes.CDLL(path))
+        _amd_at[path] = _amd_protos(ctypes.CDLL(path), old_rev=True)
     return _amd_at[path]
 
 

@@ -106,6 +106,19 @@ LAUNCH_FIELDS = ("shape", "block", "fastdiv", "pretest", "lds_bytes", "lds_nodes
                  "chunks", "spine", "sparse", "sphere_pairs", "leaf_prefetch", "shade_lds", "walk_frac", "bvh_mode",
                  "box_vnodes", "collapsed", "rebuilt")
 BVH_MODES = {"reference": 0, "sah": 1}   # rt.h RT_BVH_*
+TILE_SUM_DTYPE = np.dtype([("m2y", "<f4"), ("y", "<f4"), ("bad", "<u4"), ("pixels", "<u4")])   # rt.h rt_tile_sum
+
+
+def noise_from_tile_sums(tiles, frames, lib=None):
+    """rt_noise_from_tile_sums (host only) over TILE_SUM_DTYPE records -> dict."""
+    L = lib or _lib.amd()
+    t = np.ascontiguousarray(tiles, dtype=TILE_SUM_DTYPE)
+    s = _lib.RtNoiseStats()
+    rc = L.rt_noise_from_tile_sums(t.ctypes.data_as(ctypes.POINTER(_lib.RtTileSum)), int(t.size), int(frames),
+                                   ctypes.byref(s))
+    if rc != 0:
+        raise RTError(rc, "rt_noise_from_tile_sums: frames >= 2 required")
+    return s.as_dict()
 SHAPES = {0: "fast-lds", 1: "fast-global", 2: "link-lds", 3: "meta-lds", 4: "meta-global", 5: "link-two-level"}
 
 
@@ -264,6 +277,56 @@ class RenderContext:
         rgba = np.ascontiguousarray(rgba, dtype=np.float32)
         self._check(self._L.rt_write_image(self._h, rgba.ctypes.data_as(c_float_p)))
 
+    # -- per-pixel sample moments and the noise-target loop (rt.h rt_set_moments ...)
+    def set_moments(self, on=True):
+        """rt_set_moments: keep the per-pixel second moments beside the running mean (every launch
+        staged; the image's bits do not change).  Single-device contexts."""
+        self._check(self._L.rt_set_moments(self._h, 1 if on else 0))
+
+    def read_moments(self):
+        """rt_read_moments: M2 as [local_rows, W, 4] float32 (x, y, z and the channel sum)."""
+        out = np.empty((self.local_rows, self.width, 4), dtype=np.float32)
+        self._check(self._L.rt_read_moments(self._h, out.ctypes.data_as(c_float_p)))
+        return out
+
+    def write_moments(self, m2, n_frames):
+        """rt_write_moments: resume from a checkpoint (after write_image)."""
+        m2 = np.ascontiguousarray(m2, dtype=np.float32)
+        assert m2.size == self.local_rows * self.width * 4
+        self._check(self._L.rt_write_moments(self._h, m2.ctypes.data_as(c_float_p), int(n_frames)))
+
+    def tile_sums(self):
+        """rt_read_tile_sums: one TILE_SUM_DTYPE record per 8x8 tile, row-major."""
+        n = ctypes.c_int()
+        self._check(self._L.rt_read_tile_sums(self._h, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, dtype=TILE_SUM_DTYPE)
+        self._check(self._L.rt_read_tile_sums(self._h, out.ctypes.data_as(ctypes.POINTER(_lib.RtTileSum)), n.value,
+                                              ctypes.byref(n)))
+        return out
+
+    def noise(self):
+        """rt_noise as a dict (sum_m2y, sum_y, pixels, bad, frames, converged, noise)."""
+        s = _lib.RtNoiseStats()
+        self._check(self._L.rt_noise(self._h, ctypes.byref(s)))
+        return s.as_dict()
+
+    def render_until(self, target_noise, max_frames, batch_frames, seed=1, first_frame=1):
+        """rt_render_until -> (frames rendered, the last batch's noise dict)."""
+        s = _lib.RtNoiseStats()
+        done = ctypes.c_int()
+        self._check(self._L.rt_render_until(self._h, int(first_frame), int(max_frames), int(batch_frames),
+                                            ctypes.c_uint64(seed), float(target_noise), ctypes.byref(done),
+                                            ctypes.byref(s)))
+        return done.value, s.as_dict()
+
+    def read_samples(self):
+        """rt_debug_read_samples: the last launch's staged colours, [n_frames, local_rows, W, 4]."""
+        n = ctypes.c_int()
+        self._check(self._L.rt_debug_read_samples(self._h, None, 0, ctypes.byref(n)))
+        out = np.empty((n.value, self.local_rows, self.width, 4), dtype=np.float32)
+        self._check(self._L.rt_debug_read_samples(self._h, out.ctypes.data_as(c_float_p), out.size, ctypes.byref(n)))
+        return out
+
     # -- RCCL behind the ABI (rt.h rt_comm_*): one process per GPU
     def comm_init(self, uid, rank, world):
         """rt_comm_init with the 128-byte id rank 0 made (comm_unique_id)."""
@@ -369,6 +432,22 @@ class RaytraceExecutor:
         rf = frame_rand_factors(self.seed, self.numSamples, n)
         self.ctx.render(self.numSamples + 1, rf)
         self.numSamples += n
+
+    def raytraceUntil(self, noise, batch=16):
+        """Frames in batches of `batch` until the context's noise figure (rt_noise) is at most
+        `noise`, or samplePerPixel frames are done (no reference counterpart; the context needs
+        set_moments()).  Continues after numSamples; returns the last batch's noise dict, whose
+        'converged' says which of the two ended it."""
+        if self.numSamples == 0:
+            self._start = time.time()
+        left = self.samplePerPixel - self.numSamples
+        if left <= 0:
+            raise ValueError("raytraceUntil: setSamplePerPixel is the cap and it is reached")
+        done, stats = self.ctx.render_until(noise, left, batch, seed=self.seed, first_frame=self.numSamples + 1)
+        self.numSamples += done
+        if stats["converged"]:
+            self.samplePerPixel = self.numSamples   # sampleComplete() then runs the listeners
+        return stats
 
     def sampleComplete(self):                    # :144-156
         if not self.isSampleComplete:
