@@ -170,6 +170,10 @@ enum {
                                            chunks: the units claimed last are short (only
                                            the grouping of samples into units changes);
                                            -1 (default): 1 above 1024 BVH nodes, else 0  */
+    RT_OPTION_BOX_INTERIOR = 28,        /* compact-box kernels of the default launch: a box's
+                                           planes from one reciprocal per axis, its faces
+                                           accepted without dividing, alpha / beta divided
+                                           once for the accepted face (1)                   */
     RT_OPTION_KERNEL_VARIANT = 100,     /* A/B build: 0, 37, 30, 61 (+ stats twins)         */
     RT_OPTION_DEBUG_FLAGS = 101         /* A/B build: ablations, NOT exact                  */
 };
@@ -192,6 +196,7 @@ int rt_debug_get_option(struct rt_ctx* ctx, int option, int* value);
  *   out[16] box pre-test nodes in the walk (option box_vnodes; 0 = none)
  *   out[17] inner nodes the walk leaves out (option collapse; 0 = none)
  *   out[18] the walk's inner nodes rebuilt over the leaf sequence (option rebuild; 1/0)
+ *   out[19] division-free compact box test compiled into the kernel (option box_interior; 1/0)
  * n <= 20 ints are written; returns RT_ERR_STATE before the first render. */
 int rt_debug_last_launch(struct rt_ctx* ctx, int* out, int n);
 

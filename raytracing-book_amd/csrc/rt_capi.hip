@@ -165,6 +165,7 @@ struct rt_ctx {
     bool walk_stale = true;
     std::vector<float4> boxc_host;  // the compact box records (host copy of Device::dboxc)
     bool box_vnodes = true;         // option box_vnodes
+    bool box_interior = true;       // option box_interior
     bool zero_dir_end = true;       // option zero_dir_end (rt_kernel.hip render_stream)
     bool collapse = true;           // option collapse: the walk leaves out inner nodes (plan_collapse)
     int rebuild = 2;                // option rebuild: the walk's inner nodes rebuilt over its leaves (rebuild_inner mode)
@@ -182,7 +183,7 @@ struct rt_ctx {
     std::vector<float4> links;   // build_links(dnodes), empty when unavailable
     int fast_gen = 0;
     bool spec_ok = false;   // every child box lies inside its parent's (the near-first walk needs it)
-    int debug_flags = 0;    // env RT_DEBUG_FLAGS: ablation runs only (bit 0: Perlin -> 0.5)
+    int debug_flags = 0;    // env RT_DEBUG_FLAGS: ablation runs only (bit 0: Perlin -> 0.5; bit 3: compact boxes hit on their planes alone)
     bool uv_always = false;
     bool boxes_canon = false;   // every box has Box.java's axis-aligned face layout (dboxes[18..20])
     bool fd_ok[6] = {true, true, true, true, true, true};   // per binding: records in the fast-division regime
@@ -2193,6 +2194,7 @@ int rt_render(rt_ctx* c, int first_frame, int n_frames, const float* rand_factor
     std::memcpy(a.fl_medium, F.fl_medium, sizeof(a.fl_medium));
     std::memcpy(a.fl_rank, F.fl_rank, sizeof(a.fl_rank));
     a.debug_flags = c->debug_flags;
+    a.box_interior = c->box_interior ? 1 : 0;
     // the links the launch walks: with the box pre-test nodes (option box_vnodes) when every box has a
     // compact record and the pre-test is on (its margin is the nodes' growth: rebuilt when it changes)
     {
@@ -3261,6 +3263,7 @@ int rt_debug_set_option(rt_ctx* c, int option, int v) {
         case RT_OPTION_TL_SMALL_LDS: c->tl_small_lds = v != 0; break;
         case RT_OPTION_SHADE_LDS: c->shade_lds = v != 0; break;
         case RT_OPTION_BOX_VNODES: c->box_vnodes = v != 0; break;
+        case RT_OPTION_BOX_INTERIOR: c->box_interior = v != 0; break;
         case RT_OPTION_ZERO_DIR_END: c->zero_dir_end = v != 0; break;
         case RT_OPTION_COLLAPSE: c->collapse = v != 0; break;
         case RT_OPTION_REBUILD: if (v < 0 || v > 2) return bad(); c->rebuild = v; break;
@@ -3303,6 +3306,7 @@ int rt_debug_get_option(rt_ctx* c, int option, int* v) {
         case RT_OPTION_TL_SMALL_LDS: *v = c->tl_small_lds; break;
         case RT_OPTION_SHADE_LDS: *v = c->shade_lds; break;
         case RT_OPTION_BOX_VNODES: *v = c->box_vnodes; break;
+        case RT_OPTION_BOX_INTERIOR: *v = c->box_interior; break;
         case RT_OPTION_ZERO_DIR_END: *v = c->zero_dir_end; break;
         case RT_OPTION_COLLAPSE: *v = c->collapse; break;
         case RT_OPTION_REBUILD: *v = c->rebuild; break;

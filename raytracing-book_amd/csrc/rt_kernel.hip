@@ -357,7 +357,7 @@ __device__ __forceinline__ void render_stream(const KP& P, const float4* __restr
                     uint2 lf;
                     if (gleaf) lf = ldg_u2(gleaves + (nx & 0x7FFFFFFFu));
                     else lf = leaves[nx & 0x7FFFFFFFu];
-                    leaf_prims_t<STATS, FD, BOXC, (OPT & RT_OPT_SPAIR) != 0, STD>(P, lf.x << 16, lf.y, S.o, S.d, inv, a,
+                    leaf_prims_t<STATS, FD, BOXC, (OPT & RT_OPT_SPAIR) != 0, STD, (OPT & RT_OPT_BOXQ) != 0>(P, lf.x << 16, lf.y, S.o, S.d, inv, a,
                                                                              S.time, 0.001f, tmax, S.rf,
                                                   fx, fy, h, has, st);
                     if (STATS) {
@@ -650,7 +650,7 @@ int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int
     // the instantiations: <MINW, STATS, BLOCK, OPT> (stats twins in the A/B build only)
 #ifdef RT_AB_KNOBS
 #define RT_KERNEL(BLOCK, OPT)                                                                            \
-    (stats ? launch_persistent(render_persistent<4, true, BLOCK, OPT>, BLOCK, lds, a, d, st)                \
+    (stats ? launch_persistent(render_persistent<4, true, BLOCK, (OPT) & ~RT_OPT_BOXQ>, BLOCK, lds, a, d, st)  \
            : launch_persistent(render_persistent<4, false, BLOCK, OPT>, BLOCK, lds, a, d, st))
 #else
 #define RT_KERNEL(BLOCK, OPT) launch_persistent(render_persistent<4, false, BLOCK, OPT>, BLOCK, lds, a, d, st)
@@ -661,9 +661,14 @@ int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int
                          (a.n_sph_lds == 0 || (a.sph_lds >= 0 && a.sph_mat_lds >= 0)) &&
                          (a.n_media == 0 || a.media_lds >= 0) && (a.n_box_lds == 0 || a.box_cmp_lds >= 0) &&
                          (!a.box_all_cmp || (a.leaf_pf && a.box_mat_lds >= 0)) && a.tex_lds >= 0;
+    if (info)   // the RT_OPT_BOXQ kernels below
+        info[RT_LI_BOXQ] = (pool && !stats && a.box_interior && a.fastdiv && a.box_all_cmp && std_cfg &&
+                            shape == LINK_LDS && a.sph_pairs != 2) ? 1 : 0;
     // the link shapes x (shared-reciprocal division | plain) x (compact boxes | full box records)
 #define RT_LINK4(BLOCK, OPT)                                                                                 \
-    (a.fastdiv ? (a.box_all_cmp ? (std_cfg ? RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD | RT_OPT_BOXC | RT_OPT_STD)            \
+    (a.fastdiv ? (a.box_all_cmp ? (std_cfg ? (a.box_interior   /* not the two-level kernel: SGPR spills */          \
+                                                  ? RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD | RT_OPT_BOXC | RT_OPT_STD | (((OPT) & RT_OPT_TL) ? 0 : RT_OPT_BOXQ)) \
+                                                  : RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD | RT_OPT_BOXC | RT_OPT_STD))      \
                                            : RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD | RT_OPT_BOXC))                         \
                                 : (std_cfg ? RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD | RT_OPT_STD)                            \
                                            : RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD)))                                      \

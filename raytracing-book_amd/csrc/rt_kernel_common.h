@@ -34,6 +34,8 @@ typedef rt_kernel_args KP;
 #define RT_OPT_TL 16    // with RT_OPT_STREAM: two-level walk (top levels in LDS, the rest of the nodes global)
 #define RT_OPT_BOXC 32  // with RT_OPT_STREAM: every box has a compact record (box_test_compact), no full box test
 #define RT_OPT_SPAIR 64 // with RT_OPT_STREAM: leaves of two spheres tested at once (leaf_prims_t; most leaves are)
+#define RT_OPT_BOXQ 256 // with RT_OPT_FD, RT_OPT_BOXC and RT_OPT_STD: the compact box test with one reciprocal per
+                        // axis and no division per face (box_test_compact_q; option box_interior)
 #define RT_OPT_STD 128  // the default launch's configuration, compiled in (rt_launch_render std_config takes these
                         // kernels when it holds): staged chunks with sparse staging (P.samples, P.sflags), every
                         // medium bounded by a sphere (P.media_sph; no out-of-line boundary call), the leaf and
@@ -376,13 +378,17 @@ __device__ __forceinline__ void boxc_face(float mnx, float mny, float mnz, float
     if (I == 4) { A = make_float4(mnx, mxz, DX, 0.0f); B = make_float4(0.0f, -DZ, -(DX * DZ), __int_as_float(1)); }
     if (I == 5) { A = make_float4(mnx, mnz, DX, 0.0f); B = make_float4(0.0f, DZ, DX * DZ, __int_as_float(1)); }
 }
+// abl (A/B build, RT_DEBUG_FLAGS bit 3, never exact): a face is accepted on its plane alone, the
+// interior tests left out -- what the box block costs beyond its planes (profiles/box_test_share.md).
 __device__ __forceinline__ bool box_test_compact(float4 c0, float4 c1, float4 c2, v3 o, v3 d, float tmin, float tmax,
-                                                 float& t, int& face, float& alpha, float& beta, bool fd = false) {
+                                                 float& t, int& face, float& alpha, float& beta, bool fd = false,
+                                                 bool abl = false) {
     const float mnx = c0.x, mny = c0.y, mnz = c0.z, mxx = c0.w, mxy = c1.x, mxz = c1.y;
     const float sz = c1.z, sx = c1.w, sy = c2.x;
     // faces in the reference's order (hitting.glsl:135-146): each face's plane t, then its
     // interior test when tmin <= t <= the current ray_t.max (fd: rcp_nr / div_nr per face;
-    // sharing one reciprocal per axis kept it live across the next faces' tests: more spills)
+    // sharing one reciprocal per axis kept it live across the next faces' tests: more spills, in
+    // round 3's kernel at its 128-VGPR cap; box_test_compact_q below shares it)
     bool has = false;
 #define RT_BOXC_FACE(I, S, Q, DK, OK)                                                           \
     {                                                                                                      \
@@ -396,8 +402,8 @@ __device__ __forceinline__ bool box_test_compact(float4 c0, float4 c1, float4 c2
         if (!(fabsf(den) < 1e-8f) && (tmin <= ti && ti <= tmax)) {                                         \
             float4 A, B;                                                                                   \
             boxc_face<I>(mnx, mny, mnz, mxx, mxz, mxx - mnx, mxy - mny, mxz - mnz, A, B);                  \
-            float al, be;                                                                                  \
-            if (face_interior(A, B, o, d, ti, al, be, fd)) {                                               \
+            float al = 0.5f, be = 0.5f;                                                                    \
+            if (abl || face_interior(A, B, o, d, ti, al, be, fd)) {                                        \
                 tmax = ti;                                                                                 \
                 t = ti;                                                                                    \
                 face = I;                                                                                  \
@@ -414,6 +420,105 @@ __device__ __forceinline__ bool box_test_compact(float4 c0, float4 c1, float4 c2
     RT_BOXC_FACE(4, sy, mxy, d.y, o.y)
     RT_BOXC_FACE(5, -sy, mny, d.y, o.y)
 #undef RT_BOXC_FACE
+    return has;
+}
+
+// 0 <= RN(n / delta) <= 1 without dividing, for a numerator in face_interior's fd regime
+// (|n| >= 2^-100; delta within [2^-60, 2^20] in magnitude), where div_nr is the correctly rounded
+// quotient and cannot underflow (|q| >= 2^-120).  q >= 0: n is not zero and nothing rounds to
+// -0, so exactly when n and delta have one sign.  q <= 1: exactly when |n| <= |delta| -- the next
+// float above |delta| = m 2^e (1 <= m < 2) is |delta| + 2^(e-23), a quotient of 1 + 2^-23 / m,
+// past the tie 1 + 2^-24 that would still round down to 1.0, so no float n above |delta| does.
+// tests/test_box_interior_host.py compares this with the division over millions of pairs.
+// Both of a face's numerators at once: neither differs from delta in sign, the larger magnitude
+// is at most |delta| (fmaxf drops a NaN, which is outside the regime anyway).
+__device__ __forceinline__ bool unit_quotients(float na, float nb, float delta) {
+    const int dl = __float_as_int(delta);
+    return ((__float_as_int(na) ^ dl) | (__float_as_int(nb) ^ dl)) >= 0 && fmaxf(fabsf(na), fabsf(nb)) <= fabsf(delta);
+}
+
+// box_test_compact with fewer vector instructions (RT_OPT_BOXQ: the shared-reciprocal compact-box
+// STD kernels, option box_interior), the same bits:
+//  * planes: opposite faces (0/2 along z, 1/3 along x, 4/5 along y) have the normals s and -s, so
+//    the denominators s d_k and -(s d_k) and the numerators s Q - s o_k and -(s Q - s o_k) (a
+//    product's and a difference's rounding is sign-symmetric; a zero numerator may differ in sign,
+//    which makes t a zero of either sign, below tmin = 0.001 both ways).  v_rcp and every fma of
+//    rcp_nr / div_nr are sign-symmetric too: rcp_nr(-x) = -rcp_nr(x), and in div_nr(-n, -den, -r)
+//    q0 = (-n)(-r) = n r, fma(den, q0, -n) = -fma(-den, q0, n), fma(-e, -r, q) = fma(e, r, q).  So
+//    the opposite face's t is div_nr(s Q - s o_k, s d_k, rcp_nr(s d_k)): each t_i the bits of
+//    box_test_compact's, from one reciprocal and one s o_k per axis.
+//  * interior: a face is accepted by unit_quotients of its two numerators (face_interior's own na,
+//    nb and delta, the same operations), and only the accepted face's numerators are kept; alpha
+//    and beta are divided once after the six faces, by face_interior's fd operations on them.
+//    The numerators leave out face_interior's products with the face system's constant zeros:
+//    x - (+-0) = x and (+-0) - x = -x exactly unless x is a zero, and a zero numerator is outside
+//    the regime (next point); a non-finite pa or pb, whose product with 0 is NaN there, leaves
+//    both numerators infinite or NaN here: rejected by |n| <= |delta|, or outside the regime.
+//  * a lane whose numerator leaves the regime (below 2^-100 in magnitude, zero or NaN: a hit on a
+//    face's edge line) sets `odd`; one ballot per box then sends the wave through
+//    box_test_compact (which decides such a lane by '/'), whatever the scan found.
+__device__ __forceinline__ bool box_test_compact_q(float4 c0, float4 c1, float4 c2, v3 o, v3 d, float tmin,
+                                                   const float tmax0, float& t, int& face, float& alpha, float& beta,
+                                                   bool abl = false) {
+    const float mnx = c0.x, mny = c0.y, mnz = c0.z, mxx = c0.w, mxy = c1.x, mxz = c1.y;
+    const float sz = c1.z, sx = c1.w, sy = c2.x;
+    float tmax = tmax0, tq = 0.0f, qa = 0.0f, qb = 0.0f, qd = 1.0f;
+    int fq = -1;   // the accepted face (none yet)
+    bool odd = false;
+#define RT_BOXQ_AXIS(S, DK, OK, QA, QB, TA, TB, OKD)                                                       \
+    float TA, TB;                                                                                          \
+    bool OKD;                                                                                              \
+    {                                                                                                      \
+        const float s_ = (S), den = s_ * (DK), so = s_ * (OK), r = rcp_nr(den);                            \
+        TA = div_nr(s_ * (QA) - so, den, r);                                                               \
+        TB = div_nr(s_ * (QB) - so, den, r);                                                               \
+        OKD = !(fabsf(den) < 1e-8f);                                                                       \
+    }
+#define RT_BOXQ_FACE(I, TI, OKD)                                                                           \
+    if ((OKD) && (tmin <= (TI) && (TI) <= tmax)) {                                                         \
+        float4 A, B;                                                                                       \
+        boxc_face<I>(mnx, mny, mnz, mxx, mxz, mxx - mnx, mxy - mny, mxz - mnz, A, B);                      \
+        const int cs = __float_as_int(B.w);                                                                \
+        const float oa = (cs == 2) ? o.y : o.x, da = (cs == 2) ? d.y : d.x;                                \
+        const float ob = (cs == 0) ? o.y : o.z, db = (cs == 0) ? d.y : d.z;                                \
+        const float pa = (oa + da * (TI)) - A.x;                                                           \
+        const float pb = (ob + db * (TI)) - A.y;                                                           \
+        /* face_interior's pa B.y - pb B.x and pb A.z - pa A.w without the term whose factor is the */     \
+        /* record's constant 0 (faces 1, 3: B.y and A.z; the others: B.x and A.w) */                      \
+        const float na = ((I) == 1 || (I) == 3) ? -(pb * B.x) : pa * B.y;                                  \
+        const float nb = ((I) == 1 || (I) == 3) ? -(pa * A.w) : pb * A.z;                                  \
+        odd = odd || !(fabsf(na) >= 0x1p-100f && fabsf(nb) >= 0x1p-100f);                                  \
+        if (abl || unit_quotients(na, nb, B.z)) {                                                          \
+            tmax = (TI);                                                                                   \
+            tq = (TI);                                                                                     \
+            fq = I;                                                                                        \
+            qa = na;                                                                                       \
+            qb = nb;                                                                                       \
+            qd = B.z;                                                                                      \
+        }                                                                                                  \
+    }
+    // faces in the reference's order (hitting.glsl:135-146) under its sequential ray_t test; the y
+    // planes after faces 0-3, so at most four plane parameters are live at once
+    RT_BOXQ_AXIS(sz, d.z, o.z, mxz, mnz, t0, t2, okz)
+    RT_BOXQ_AXIS(sx, d.x, o.x, mxx, mnx, t1, t3, okx)
+    RT_BOXQ_FACE(0, t0, okz)
+    RT_BOXQ_FACE(1, t1, okx)
+    RT_BOXQ_FACE(2, t2, okz)
+    RT_BOXQ_FACE(3, t3, okx)
+    RT_BOXQ_AXIS(sy, d.y, o.y, mxy, mny, t4, t5, oky)
+    RT_BOXQ_FACE(4, t4, oky)
+    RT_BOXQ_FACE(5, t5, oky)
+#undef RT_BOXQ_AXIS
+#undef RT_BOXQ_FACE
+    if (!abl && __ballot(odd) != 0) return box_test_compact(c0, c1, c2, o, d, tmin, tmax0, t, face, alpha, beta, true);
+    const bool has = fq >= 0;
+    if (has) {
+        const float r = rcp_nr(qd);
+        t = tq;
+        face = fq;
+        alpha = abl ? 0.5f : div_nr(qa, qd, r);
+        beta = abl ? 0.5f : div_nr(qb, qd, r);
+    }
     return has;
 }
 
@@ -602,7 +707,8 @@ __device__ __forceinline__ bool aabb_pk(float4 n0, float4 n1, v3 o, v3 inv, floa
 
 // The two prims of a leaf (compute.glsl:247-256), left then right.
 // FD: the shared-reciprocal divisions (rcp_nr / div_nr; FD kernels only).
-template <bool STATS, bool FD, bool BOXC = false, bool SPAIR = false, bool STD = false>
+// BOXQ (RT_OPT_BOXQ, with FD, BOXC and STD): the compact box test as box_test_compact_q.
+template <bool STATS, bool FD, bool BOXC = false, bool SPAIR = false, bool STD = false, bool BOXQ = false>
 __device__ __forceinline__ void leaf_prims_t(const KP& P, uint32_t meta, uint32_t prims, v3 o, v3 d, v3 inv, float a,
                                              float time, float tmin, float& tmax, float& rf, float px, float py, Hit& h,
                                              bool& has, unsigned long long* st) {
@@ -743,8 +849,15 @@ __device__ __forceinline__ void leaf_prims_t(const KP& P, uint32_t meta, uint32_
                                 make_float4(r0.z - m, r1.y + m, 0.0f, 0.0f), o, inv, tmin, tmax);
             }
             if (maybe) {
-                if constexpr (BOXC)
-                    hit = box_test_compact(r0, r1, r2, o, d, tmin, tmax, t, face, al, be, fd);
+#ifdef RT_AB_KNOBS
+                const bool abl = (P.debug_flags & 8) != 0;   // ablation only (A/B build, RT_DEBUG_FLAGS), never exact
+#else
+                constexpr bool abl = false;
+#endif
+                if constexpr (BOXC && BOXQ && FD && STD && !STATS)
+                    hit = box_test_compact_q(r0, r1, r2, o, d, tmin, tmax, t, face, al, be, abl);
+                else if constexpr (BOXC)
+                    hit = box_test_compact(r0, r1, r2, o, d, tmin, tmax, t, face, al, be, fd, abl);
                 else
                     hit = box_test(P.dboxes + RT_DBOX_F4 * ix, o, d, tmin, tmax, t, face, al, be, fd);
             }
