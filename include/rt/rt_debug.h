@@ -40,7 +40,7 @@ int rt_debug_link_nodes(const void* bvh, size_t nbytes, void* out, size_t out_ca
 int rt_debug_link_nodes_vbox(const void* bvh, size_t nbytes, const float* vbox, int n_box, void* out,
                              size_t out_cap, int* n_f4, int* n_nodes);
 /* The link-format nodes of `bvh` as the walk of a context uses them: with rebuild != 0 the inner
- * nodes rebuilt over the leaf sequence (option rebuild, rt_capi.hip rebuild_inner), then the node
+ * nodes rebuilt over the leaf sequence (option rebuild, rt_prep.cpp rebuild_inner), then the node
  * collapse of option collapse (plan_collapse) planned for camera `cam` (rt_camera_ubo, 28
  * floats) and a width x height image; drop (may be NULL) gets one byte per threaded node of that
  * tree (1 = left out), *n_dropped their count.  Host-side, no device needed
@@ -65,7 +65,7 @@ int rt_debug_sphere_pair_leaves(const void* bvh, size_t nbytes, int* permille);
 int rt_debug_deinterleave(const float* gathered, int width, int height, int world, int stripe_rows, float* out);
 
 /* Host-only: the boxes' 48-byte records rt_upload_buffer(RT_BIND_BOXES) builds
- * (rt_capi.hip box_record: 3 float4 per box; float4[2].y = 1 for a compact record,
+ * (rt_prep.cpp box_record: 3 float4 per box; float4[2].y = 1 for a compact record,
  * whose faces the kernel rebuilds from it) and how many are compact. */
 int rt_debug_box_records(const void* boxes, size_t nbytes, void* out, size_t out_cap, int* n_compact);
 
@@ -160,10 +160,10 @@ enum {
                                            miss colour its next bounce would give (1)       */
     RT_OPTION_COLLAPSE = 25,            /* the link walk leaves out the inner nodes whose
                                            tests a grid of camera rays says cost more than
-                                           they save (rt_capi.hip plan_collapse) (1)        */
+                                           they save (rt_prep.cpp plan_collapse) (1)        */
     RT_OPTION_REBUILD = 26,             /* the link walk's inner nodes rebuilt over the
                                            reference's leaf sequence (joined boxes: the same
-                                           leaves, order and ray_t; rt_capi.hip
+                                           leaves, order and ray_t; rt_prep.cpp
                                            rebuild_inner): 1 greedy surface-area splits,
                                            2 the least summed inner-box area (default); 0 off */
     RT_OPTION_TAIL_CHUNKS = 27,         /* staged launches end with this many one-frame

@@ -1,0 +1,241 @@
+// rt_debug_host.cpp — the C ABI's entries that need no context and no device: the stripe
+// arithmetic and frame factors of rt.h, and rt_debug.h's views of the host-only scene
+// preparation (rt_prep.h).  Plain C++, built once and linked into both libraries; with
+// rt_prep.cpp it links into a stand-alone program (tools/fuzz).
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+#include <vector>
+
+#include "rt/rt.h"
+#include "rt/rt_debug.h"
+#include "rt/rt_types.h"
+#include "rt_prep.h"
+#include "bvh_sah.h"
+
+using namespace rt_impl;
+
+extern "C" {
+
+int rt_local_rows(int height, int rank, int world, int stripe_rows) { return local_rows_of(height, rank, world, stripe_rows); }
+int rt_padded_local_rows(int height, int world, int stripe_rows) {
+    if (height <= 0 || world <= 0 || stripe_rows <= 0) return 0;
+    return padded_rows_of(height, world, stripe_rows);
+}
+
+int rt_noise_from_tile_sums(const rt_tile_sum* tiles, int n_tiles, int frames, rt_noise_stats* out) {
+    if (!out || n_tiles < 0 || (n_tiles > 0 && !tiles) || frames < 2) return RT_ERR_INVALID_ARG;
+    rt_noise_stats s;
+    std::memset(&s, 0, sizeof(s));
+    for (int i = 0; i < n_tiles; i++) {   // in tile order, in double: the figure depends on the tiles alone
+        s.sum_m2y += (double)tiles[i].m2y;
+        s.sum_y += (double)tiles[i].y;
+        s.pixels += tiles[i].pixels;
+        s.bad += tiles[i].bad;
+    }
+    s.frames = frames;
+    const double p = (double)(s.pixels - s.bad);
+    const double num = std::sqrt(std::max(0.0, s.sum_m2y / ((double)frames * ((double)frames - 1.0))) * p);
+    if (s.sum_y == 0.0) s.noise = num == 0.0 ? 0.0 : (double)INFINITY;
+    else s.noise = num / s.sum_y;
+    *out = s;
+    return RT_OK;
+}
+
+int rt_deinterleave_rows(const float* gathered, int width, int height, int world, int stripe_rows, float* out) {
+    if (!gathered || !out || width <= 0 || height <= 0 || world < 1 || stripe_rows < 1) return RT_ERR_INVALID_ARG;
+    int padded = padded_rows_of(height, world, stripe_rows);
+    int n_stripes = (height + stripe_rows - 1) / stripe_rows;
+    for (int k = 0; k < world; k++) {
+        size_t lr = 0;
+        for (int s = k; s < n_stripes; s += world)
+            for (int y = s * stripe_rows; y < std::min(height, (s + 1) * stripe_rows); y++, lr++)
+                std::memcpy(out + (size_t)y * width * 4, gathered + ((size_t)k * padded + lr) * width * 4,
+                            (size_t)width * 16);
+    }
+    return RT_OK;
+}
+
+float rt_frame_rand_factor(uint64_t seed, uint64_t frame_index) {
+    uint64_t z = seed + (frame_index + 1) * 0x9E3779B97F4A7C15ULL;
+    z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
+    z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
+    z ^= z >> 31;
+    return (float)(uint32_t)(z >> 40) / 16777216.0f;
+}
+
+int rt_debug_threaded_bvh(const void* nodes, size_t nbytes, void* out, size_t out_cap, int* n_out) {
+    if (!nodes || !n_out || nbytes % sizeof(rt_bvh_node)) return RT_ERR_INVALID_ARG;
+    std::vector<rt_dnode> dn;
+    int r = thread_bvh((const rt_bvh_node*)nodes, (int)(nbytes / sizeof(rt_bvh_node)), dn, nullptr);
+    if (r) return r;
+    *n_out = (int)dn.size();
+    if (out) {
+        if (out_cap < dn.size() * sizeof(rt_dnode)) return RT_ERR_INVALID_ARG;
+        if (!dn.empty()) std::memcpy(out, dn.data(), dn.size() * sizeof(rt_dnode));
+    }
+    return RT_OK;
+}
+
+int rt_debug_deinterleave(const float* gathered, int width, int height, int world, int stripe_rows, float* out) {
+    if (!gathered || !out || width <= 0 || height <= 0 || world < 1 || stripe_rows < 1) return RT_ERR_INVALID_ARG;
+    const int padded = padded_rows_of(height, world, stripe_rows);
+    for (int y = 0; y < height; y++) {   // deinterleave_kernel's indexing, one row at a time
+        int k, lr;
+        rt_gathered_row(y, world, stripe_rows, &k, &lr);
+        std::memcpy(out + (size_t)y * width * 4, gathered + ((size_t)k * padded + lr) * width * 4, (size_t)width * 16);
+    }
+    return RT_OK;
+}
+
+int rt_debug_box_records(const void* boxes, size_t nbytes, void* out, size_t out_cap, int* n_compact) {
+    if (!boxes || !n_compact || nbytes % sizeof(rt_box)) return RT_ERR_INVALID_ARG;
+    const size_t nb = nbytes / sizeof(rt_box);
+    if (out && out_cap < nb * RT_BOXC_F4 * sizeof(float4)) return RT_ERR_INVALID_ARG;
+    // the upload's own path (rt_upload_buffer(RT_BIND_BOXES) calls prep_boxes too)
+    const BoxPrep P = prep_boxes((const rt_quad*)boxes, nb);
+    const std::vector<float4>& recs = P.boxc;
+    *n_compact = P.n_compact;
+    if (out && !recs.empty()) std::memcpy(out, recs.data(), recs.size() * sizeof(float4));
+    return RT_OK;
+}
+
+int rt_debug_link_nodes_vbox(const void* bvh, size_t nbytes, const float* vbox, int n_box, void* out,
+                             size_t out_cap, int* n_f4, int* n_nodes) {
+    if (!bvh || !n_f4 || !n_nodes || nbytes % sizeof(rt_bvh_node) || n_box < 0 || (n_box && !vbox))
+        return RT_ERR_INVALID_ARG;
+    std::vector<rt_dnode> dn;
+    int r = thread_bvh((const rt_bvh_node*)bvh, (int)(nbytes / sizeof(rt_bvh_node)), dn, nullptr);
+    if (r) return r;
+    const std::vector<float> vb(vbox, vbox + 6 * (size_t)n_box);
+    const std::vector<float4> L = build_links(dn, &vb, n_nodes);
+    *n_f4 = (int)L.size();
+    if (out) {
+        if (out_cap < L.size() * sizeof(float4)) return RT_ERR_INVALID_ARG;
+        if (!L.empty()) std::memcpy(out, L.data(), L.size() * sizeof(float4));
+    }
+    return RT_OK;
+}
+
+int rt_debug_collapse_links(const void* bvh, size_t nbytes, const float cam[28], int width, int height, int rebuild,
+                            void* out, size_t out_cap, int* n_f4, uint8_t* drop, size_t drop_cap, int* n_dropped) {
+    if (!bvh || !cam || !n_f4 || !n_dropped || nbytes % sizeof(rt_bvh_node)) return RT_ERR_INVALID_ARG;
+    std::vector<rt_dnode> dn;
+    int r = thread_bvh((const rt_bvh_node*)bvh, (int)(nbytes / sizeof(rt_bvh_node)), dn, nullptr);
+    if (r) return r;
+    if (rebuild) {
+        std::vector<rt_dnode> rb = rebuild_inner(dn, rebuild);
+        if (!rb.empty()) dn.swap(rb);
+    }
+    rt_camera_ubo cu;
+    std::memcpy(&cu, cam, sizeof(cu));
+    const std::vector<uint8_t> d = plan_collapse(dn, cu, width, height);
+    int nd = 0;
+    for (uint8_t x : d) nd += x;
+    *n_dropped = nd;
+    int nn = 0;
+    const std::vector<float4> L = build_links(dn, nullptr, &nn, &d);
+    *n_f4 = (int)L.size();
+    if (out) {
+        if (out_cap < L.size() * sizeof(float4)) return RT_ERR_INVALID_ARG;
+        if (!L.empty()) std::memcpy(out, L.data(), L.size() * sizeof(float4));
+    }
+    if (drop) {
+        if (drop_cap < d.size()) return RT_ERR_INVALID_ARG;
+        if (!d.empty()) std::memcpy(drop, d.data(), d.size());
+    }
+    return RT_OK;
+}
+
+int rt_debug_link_nodes(const void* bvh, size_t nbytes, void* out, size_t out_cap, int* n_f4) {
+    if (!bvh || !n_f4 || nbytes % sizeof(rt_bvh_node)) return RT_ERR_INVALID_ARG;
+    std::vector<rt_dnode> dn;
+    int r = thread_bvh((const rt_bvh_node*)bvh, (int)(nbytes / sizeof(rt_bvh_node)), dn, nullptr);
+    if (r) return r;
+    const std::vector<float4> L = build_links(dn);
+    *n_f4 = (int)L.size();
+    if (out) {
+        if (out_cap < L.size() * sizeof(float4)) return RT_ERR_INVALID_ARG;
+        if (!L.empty()) std::memcpy(out, L.data(), L.size() * sizeof(float4));
+    }
+    return RT_OK;
+}
+
+int rt_debug_perlin_pack(const float* texels, int w, int h, void* out, size_t out_cap) {
+    if (!texels || w <= 0 || h <= 0) return RT_ERR_INVALID_ARG;
+    std::vector<float4> pk;
+    if (!perlin_pack(texels, w, h, pk)) return 0;
+    if (out) {
+        if (out_cap < pk.size() * sizeof(float4)) return RT_ERR_INVALID_ARG;
+        if (!pk.empty()) std::memcpy(out, pk.data(), pk.size() * sizeof(float4));
+    }
+    return 1;
+}
+
+int rt_debug_sphere_pair_leaves(const void* bvh, size_t nbytes, int* permille) {
+    if (!bvh || !permille || nbytes % sizeof(rt_bvh_node)) return RT_ERR_INVALID_ARG;
+    std::vector<rt_dnode> dn;
+    int r = thread_bvh((const rt_bvh_node*)bvh, (int)(nbytes / sizeof(rt_bvh_node)), dn, nullptr);
+    if (r) return r;
+    *permille = pair_leaves_permille(build_links(dn), (int)dn.size());
+    return RT_OK;
+}
+
+int rt_debug_fast_tables(const void* bvh, size_t nbytes, const void* quads, size_t qbytes, const void* boxes,
+                         size_t bbytes, int n_spheres, void* nodes_out, size_t nodes_cap, int* n_per_octant,
+                         uint32_t* info_out, size_t info_cap, int* slots_out, int* n_slots) {
+    if (!bvh || nbytes % sizeof(rt_bvh_node) || qbytes % sizeof(rt_quad) || bbytes % sizeof(rt_box) || n_spheres < 0 ||
+        !n_per_octant || !n_slots || (qbytes && !quads) || (bbytes && !boxes))
+        return RT_ERR_INVALID_ARG;
+    std::vector<rt_dnode> dn;
+    int r = thread_bvh((const rt_bvh_node*)bvh, (int)(nbytes / sizeof(rt_bvh_node)), dn, nullptr);
+    if (r) return r;
+    FastTables F = build_fast(dn, (size_t)n_spheres, (const rt_quad*)quads, qbytes / sizeof(rt_quad),
+                              (const rt_box*)boxes, bbytes / sizeof(rt_box));
+    *n_per_octant = F.n_per;
+    *n_slots = F.fm_n;
+    if (nodes_out) {
+        if (nodes_cap < F.nodes.size() * sizeof(rt_dnode)) return RT_ERR_INVALID_ARG;
+        if (!F.nodes.empty()) std::memcpy(nodes_out, F.nodes.data(), F.nodes.size() * sizeof(rt_dnode));
+    }
+    if (info_out) {
+        if (info_cap < F.info.size() * sizeof(uint32_t)) return RT_ERR_INVALID_ARG;
+        if (!F.info.empty()) std::memcpy(info_out, F.info.data(), F.info.size() * sizeof(uint32_t));
+    }
+    if (slots_out)
+        for (int j = 0; j < F.fm_n; j++) {
+            slots_out[4 * j + 0] = F.fm_medium[j];
+            slots_out[4 * j + 1] = F.fm_leaf[j];
+            slots_out[4 * j + 2] = F.fm_track[j];
+            slots_out[4 * j + 3] = F.fm_flags[j];
+        }
+    return (F.ok && boxes_nest(dn)) ? 1 : 0;
+}
+
+int rt_debug_build_sah_bvh(const void* spheres, size_t sph_bytes, const void* quads, size_t quad_bytes,
+                           const void* media, size_t med_bytes, const void* boxes, size_t box_bytes,
+                           const void* bvh, size_t bvh_bytes, int order, const float eye[3],
+                           float prim_cost, void* out, size_t out_cap, size_t* nbytes) {
+    if (!nbytes || (bvh_bytes && !bvh) || order < 0 || order > 2 || !(prim_cost > 0.0f)) return RT_ERR_INVALID_ARG;
+    rt_sah::Input in;
+    in.sph = (const rt_sphere*)spheres;
+    in.n_sph = spheres ? sph_bytes / sizeof(rt_sphere) : 0;
+    in.quad = (const rt_quad*)quads;
+    in.n_quad = quads ? quad_bytes / sizeof(rt_quad) : 0;
+    in.med = (const rt_medium*)media;
+    in.n_med = media ? med_bytes / sizeof(rt_medium) : 0;
+    in.box = (const rt_box*)boxes;
+    in.n_box = boxes ? box_bytes / sizeof(rt_box) : 0;
+    in.ref = (const rt_bvh_node*)bvh;
+    in.n_ref = bvh_bytes / sizeof(rt_bvh_node);
+    std::vector<rt_bvh_node> t;
+    rt_sah::Builder b(in, order, eye, prim_cost);
+    if (!b.build(t)) return RT_ERR_INVALID_ARG;
+    *nbytes = t.size() * sizeof(rt_bvh_node);
+    if (!out) return RT_OK;
+    if (out_cap < *nbytes) return RT_ERR_LIMIT;
+    std::memcpy(out, t.data(), *nbytes);
+    return RT_OK;
+}
+
+}  // extern "C"

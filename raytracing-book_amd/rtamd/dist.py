@@ -99,7 +99,7 @@ def native_gather(ctx, rank, world, timeout_ms=None):
     uid, err = box[0]
     if uid is None:
         raise RuntimeError(f"rank 0 could not make an RCCL communicator id: {err}")
-    # rt_comm_init's own preconditions (rt_capi.hip: a 1-device context partitioned as (rank, world))
+    # rt_comm_init's own preconditions (rt_comm.hip: a 1-device context partitioned as (rank, world))
     _agree(len(getattr(ctx, "devices", (0,))) == 1 and getattr(ctx, "rank", rank) == rank
            and getattr(ctx, "world", world) == world, "the rt_comm_init preconditions")
     ok = True

@@ -14,7 +14,7 @@ hit tests they target (hitting.glsl:90-146):
   * plane t at, just below and just above tmin = 0.001 (inclusive for quads,
     strict for spheres);
   * scenes scaled so their extent sits just inside / just past 2^20, where the
-    shared-reciprocal division stops applying (rt_capi.hip fd_coord);
+    shared-reciprocal division stops applying (rt_prep.cpp fd_coord);
   * BVHs beyond the round-2 link-format cap of 2047 nodes, one in LDS (~4000
     nodes) and one that needs the two-level walk (~9000 nodes);
   * walks that start past the root's right spine (rt_kernel.hip spine_entry): ray
@@ -172,7 +172,7 @@ def sphere_cloud(n, seed, W=64, H=48, boxes=True):
 
 def spine_box(scene):
     """The intersection of the boxes on the threaded BVH's right spine (root, its right
-    child, ... to the first leaf): what rt_capi.hip plan_spine intersects."""
+    child, ... to the first leaf): what rt_prep.cpp plan_spine intersects."""
     import ctypes
     L = rtamd.amd()
     bvh = scene.buffers[1]

@@ -32,7 +32,7 @@ def leaves(rec):
 
 def leaf_slots(rec):
     """Multiset of prim slots a walk tests, with the link format's rule: a singleton leaf
-    tests a medium twice, anything else once (rt_capi.hip thread_bvh)."""
+    tests a medium twice, anything else once (rt_prep.cpp thread_bvh)."""
     out = {}
     for lo, r in leaves(rec):
         if lo == r and (lo & 0xFFFF) != 3:

@@ -1,4 +1,4 @@
-"""Host-side tables of the exact near-first walk (rt_capi.hip build_fast,
+"""Host-side tables of the exact near-first walk (rt_prep.cpp build_fast,
 RT_KERNEL_VARIANT=60), through rt_debug_fast_tables — no GPU needed.
 
 * each of the 8 octant layouts is a threaded pre-order of one SAH tree that

@@ -101,7 +101,7 @@ def test_two_level_walk_forced(gpu, cap, tll, small):
     ref = oracle(case)
     out, info = render(case, {"lds_node_cap": cap, "tl_leaf_lds": tll, "tl_small_lds": small})
     assert info["shape_name"] == "link-two-level" and info["lds_nodes"] == cap // 32, info
-    assert info["walk_frac"] == 32, info   # the two-level rounds (rt_capi.hip LDS plan)
+    assert info["walk_frac"] == 32, info   # the two-level rounds (rt_plan.cpp plan_lds)
     assert bit_equal(out, ref), mismatch_report(out, ref)
 
 
@@ -170,7 +170,7 @@ def test_release_library_has_no_ab_options(gpu):
 
 @pytest.mark.parametrize("sid,want", [(6, 8), (0, 32), (8, 48)])
 def test_walk_threshold_by_bvh_size(gpu, sid, want):
-    """walk_frac 0 (the default) picks the walk round threshold by BVH size (rt_capi.hip
+    """walk_frac 0 (the default) picks the walk round threshold by BVH size (rt_prep.cpp
     walk_frac_for: 8/64 up to 64 nodes, 32 up to 1024, 48 above; measured per scene); explicit
     values override it.  Rounds only regroup lanes: the same bits at the default, 8 and 48."""
     scene = rtamd.Scene(sid, 96, 64, seed=1)
@@ -190,7 +190,7 @@ def test_walk_threshold_by_bvh_size(gpu, sid, want):
 
 def test_shading_threshold_by_kernel(gpu):
     """sm_frac 0 (the default) picks the threshold by kernel (50/64 for the compact-box kernels,
-    56/64 else, rt_capi.hip); explicit values 1..64 override it and anything else is refused.
+    56/64 else, rt_capi.hip rt_render); explicit values 1..64 override it and anything else is refused.
     The threshold only regroups which lanes shade together: scene 8 (compact boxes) and scene 6
     render the same bits at 0, 50 and 56."""
     ctx = rtamd.RenderContext()

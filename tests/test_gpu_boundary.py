@@ -198,7 +198,7 @@ def test_bound_torch_image_and_stream(gpu):
 VARIANTS = [0, 37, 30, 61]   # streamed batched pooled samples (default), one pixel per lane (round-1 default), threaded meta walk, exact near-first walk
 
 
-# work splits (rt_capi.hip rt_render; rt_debug.h RT_OPTION_*): one unit per tile with all
+# work splits (rt_plan.cpp plan_split, plan_chunks; rt_debug.h RT_OPTION_*): one unit per tile with all
 # frames (folded per wave), ordered frame chunks handed over between waves, staged chunks
 # (the default)
 SPLITS = {

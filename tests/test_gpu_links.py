@@ -1,5 +1,5 @@
 """The link-format node loop of the A/B build's variant 37 (rt_kernel.hip trace;
-nodes from rt_capi.hip build_links) against the threaded meta-word walk (30).
+nodes from rt_prep.cpp build_links) against the threaded meta-word walk (30).
 
 It walks the reference's threaded BVH in the same node order as variant 30,
 only with explicit hit / miss successors and packed slab arithmetic, so the

@@ -214,7 +214,7 @@ def test_box_pretest_nodes_match_oracle(gpu, opts, expect):
 
 def test_collapsed_walk_matches_oracle_and_follows_the_camera(gpu):
     """Round 5: the link walk leaves out the inner nodes a grid of camera rays says cost more tests
-    than they save (option collapse, on by default; rt_capi.hip plan_collapse).  Bit for bit against
+    than they save (option collapse, on by default; rt_prep.cpp plan_collapse).  Bit for bit against
     the oracle; the plan is the host's for this camera and image size, and a moved camera re-plans
     it (the launch reports the count the context-free planner gives for the new camera)."""
     from test_link_nodes import collapse_links

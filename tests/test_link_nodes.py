@@ -1,4 +1,4 @@
-"""The link-format BVH the default kernel walks (rt_capi.hip build_links,
+"""The link-format BVH the default kernel walks (rt_prep.cpp build_links,
 rt_device.h RT_LINK_*; rt_kernel.hip link_walk) — host-side, no GPU needed.
 
 Every node keeps its threaded node's box and is placed breadth-first (the
@@ -274,7 +274,7 @@ def collapse_links(scene, width=1920, height=1080, cam=None, rebuild=0):
 
 def nested_hits(tn, rng, p):
     """A random box-hit pattern in which a node hits only where its parent does (boxes nest, and the
-    slab test is monotone in the box: rt_capi.hip plan_collapse)."""
+    slab test is monotone in the box: rt_prep.cpp plan_collapse)."""
     hits = np.zeros(len(tn), bool)
     hits[0] = rng.random() < max(p, 0.5)
     for k, nd in enumerate(tn):
@@ -427,7 +427,7 @@ def test_rebuilt_inner_nodes_test_the_same_leaves(sid, rebuild):
     (option collapse): for rays through the scene -- some with a zero direction component (1/dir
     = +-inf), ray_t.max shrinking at some leaves -- the walk over the links tests the reference
     tree's leaves in the same order under the same ray_t.max.  Nothing about the inner nodes
-    matters but that their boxes hold the leaves' (rt_capi.hip rebuild_inner)."""
+    matters but that their boxes hold the leaves' (rt_prep.cpp rebuild_inner)."""
     scene = rtamd.Scene(sid, 1920, 1080, seed=1)
     tn = threaded(scene)
     n = len(tn)

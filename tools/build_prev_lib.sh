@@ -17,6 +17,7 @@ FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -ffp-contract=off -fno-slp-vectorize
 INC="-I$TMP/include -I$ROOT/include -I$PKG/csrc -I$PKG/host"
 /opt/rocm/bin/hipcc $FLAGS $INC -c -o "$TMP/k.o" "$TMP/rt_kernel.hip"
 mkdir -p "$PKG/lib/prev"
-/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$PKG/lib/prev/librtamd.so" "$TMP/k.o" "$PKG/build/obj/rt_moments.o" "$PKG/build/obj/rt_capi.o"
+# the working tree's C-ABI objects: the Makefile holds the list (make builds them)
+/opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$PKG/lib/prev/librtamd.so" "$TMP/k.o" $(make -s -C "$PKG" print-abi-objs)
 rm -rf "$TMP"
 echo "built $PKG/lib/prev/librtamd.so from $REV"

@@ -29,6 +29,7 @@ def main():
     ap.add_argument("--depth", type=int, default=5)
     ap.add_argument("--clouds", default="")
     ap.add_argument("--options", default="{}")
+    ap.add_argument("--last-launch", action="store_true", help="print each library's rt_debug_last_launch")
     a = ap.parse_args()
     libs = a.libs.split(",")
     opts = json.loads(a.options)
@@ -65,12 +66,15 @@ def main():
                         same = np.array_equal(img.view(np.uint32), ref.view(np.uint32))
                         print(f"scene {sid} {libs[k]}: bits {'identical' if same else 'DIFFER'} to {libs[0]}",
                               flush=True)
+                    if a.last_launch:   # what the planner chose (rt_debug_last_launch)
+                        print(f"scene {sid} {libs[k]}: last_launch {json.dumps(c.last_launch(), sort_keys=True)}",
+                              flush=True)
                     continue
                 times[k].append(ns / 1e6)
         samples = a.width * a.height * a.frames
         for k, lib in enumerate(libs):
             med = statistics.median(times[k])
-            print(f"scene {sid} {lib}: median {med:.3f} ms  min {min(times[k]):.3f} ms  -> "
+            print(f"scene {sid} {lib}: median {med:.3f} ms  min {min(times[k]):.3f} ms  max {max(times[k]):.3f} ms  -> "
                   f"{samples / med / 1e3:.1f} Msamples/s", flush=True)
         for c in ctxs:
             c.close()

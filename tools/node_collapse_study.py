@@ -198,7 +198,7 @@ def main():
         e = area_rule(kids, box, r)
         c = cost(kids, Hh, walks, e)
         print(f"  area rule {r:.1f}: {c / walks:.2f} per walk ({100 * (c / base - 1):+.1f}%), {len(e)} left out")
-    # the kernel already skips the spine (rt_capi.hip plan_spine: the first nodes of the right-most
+    # the kernel already skips the spine (rt_prep.cpp plan_spine: the first nodes of the right-most
     # chain, hits for a walk starting inside them; scene 8: 11): the gain over that
     chain, nd = [], 0
     while nd in kids and len(chain) < a.spine:
