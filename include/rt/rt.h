@@ -227,6 +227,57 @@ int rt_noise(rt_ctx* ctx, rt_noise_stats* out);
 int rt_render_until(rt_ctx* ctx, int first_frame, int max_frames, int batch_frames, uint64_t seed,
                     float target_noise, int* frames_done, rt_noise_stats* last);
 
+/* ---- Adaptive sampling: tile masks, per-tile frame counts, a per-tile stopping rule -----------
+ * A sample's bits depend on its pixel, its frame and the scene alone, so a tile whose sampling
+ * stopped after frame n holds, pixel for pixel and in its moments, the bits of a plain n-frame
+ * render.  Single-device contexts without rt_set_partition (RT_ERR_STATE otherwise).
+ *
+ * active: one byte per 8x8 tile of the image, tiles row-major, ceil(W/8) per row (the tiles of
+ * rt_read_tile_sums); NULL = all tiles again.  While set, rt_render samples only the pixels of
+ * tiles whose byte is non-zero; every other pixel's image and moments words are not written.
+ * n_tiles must match the image (RT_ERR_INVALID_ARG); rt_resize clears the mask.  With no byte
+ * set rt_render launches nothing and returns RT_OK. */
+int rt_set_active_tiles(rt_ctx* ctx, const uint8_t* active, int n_tiles);
+/* One frame count per tile: the frames 1 .. n the tile holds, 0 = invalid.  For each tile a
+ * launch samples, first_frame == 1 sets its count to n_frames, first_frame == count + 1 adds
+ * n_frames, anything else sets 0; the other tiles keep theirs.  rt_write_image,
+ * rt_bind_device_image and rt_resize set every count to 0, rt_write_moments(n) to n.  The
+ * moments are valid when every count is >= 1.  frames may be NULL to query *n_tiles;
+ * RT_ERR_LIMIT if cap is short. */
+int rt_read_tile_frames(rt_ctx* ctx, int32_t* frames, int cap, int* n_tiles);
+/* Resume a checkpoint whose tiles stopped at different frames: after rt_write_image and
+ * rt_write_moments, the counts (each >= 0). */
+int rt_write_tile_frames(rt_ctx* ctx, const int32_t* frames, int n_tiles);
+/* Host only.  rt_noise_from_tile_sums for tiles with their own frame counts; in double, the
+ * tiles in order, with P = pixels - bad over all tiles:
+ *   noise = sqrt(max(0, sum_t m2y_t / (n_t (n_t - 1))) * P) / sum_y,   every n_t >= 2;
+ * out->frames = max n_t, out->sum_m2y the plain sum.  rt_noise uses it when the counts differ. */
+int rt_noise_from_tile_sums_frames(const rt_tile_sum* tiles, const int32_t* frames, int n_tiles,
+                                   rt_noise_stats* out);
+/* Host only, pure.  frames = F, the frames every active tile holds.  In double, tiles in index
+ * order, P_t = pixels_t - bad_t:
+ *   ybar = sum_t y_t / sum_t P_t over ALL tiles (0 when no good pixel);
+ *   lim  = (double)target * ybar;
+ *   v_t  = (double)m2y_t / ((double)F * (F - 1)) / P_t;
+ * an active tile stays active unless F >= min_frames and (P_t == 0 or v_t <= lim * lim).  An
+ * inactive tile stays inactive (active_in NULL: all active).  If every tile satisfies
+ * v_t <= lim * lim, the rt_noise figure is <= target.  min_frames >= 2 guards a dark tile
+ * against stopping before any path has found the light: with all its samples zero so far its
+ * variance estimate is 0, which passes any limit.  n_active may be NULL. */
+int rt_adaptive_select(const rt_tile_sum* tiles, const uint8_t* active_in, int n_tiles, int frames,
+                       int min_frames, float target, uint8_t* active_out, int* n_active);
+/* rt_render_until with the rule above between batches: frames first_frame, first_frame + 1, ...
+ * in batches of batch_frames with rt_frame_rand_factor(seed, f - 1); after each batch rt_sync,
+ * the tile sums, rt_adaptive_select, and the next batch renders the tiles still active.  Stops
+ * when none is (last->converged = 1) or after max_frames (0).  A stopped tile never restarts:
+ * its count (rt_read_tile_frames) is the frame at which it stopped.  last = rt_noise's figures
+ * at the end; *frames_done = the frames of the longest-sampled tiles rendered by this call.
+ * first_frame is 1, or the largest count + 1 with valid counts (RT_ERR_STATE otherwise); tiles
+ * with a smaller count are already stopped.  Needs rt_set_moments(ctx, 1); no caller mask may
+ * be set (RT_ERR_STATE) and none is left set.  Not pipelined. */
+int rt_render_adaptive(rt_ctx* ctx, int first_frame, int max_frames, int batch_frames, int min_frames,
+                       uint64_t seed, float target_noise, int* frames_done, rt_noise_stats* last);
+
 /* Per-frame u_rand_factor for frame index f (0-based) of a seeded render:
  * top 24 bits of splitmix64(seed, f) / 2^24, in [0,1).  Stands in for the
  * reference's (float)Math.random() per frame (RaytraceExecutor.java:124). */

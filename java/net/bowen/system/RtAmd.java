@@ -104,6 +104,18 @@ public final class RtAmd implements AutoCloseable {
     private static final MethodHandle NOISE = fn("rt_noise", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS));
     private static final MethodHandle RENDER_UNTIL = fn("rt_render_until",
             FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_LONG, JAVA_FLOAT, ADDRESS, ADDRESS));
+    private static final MethodHandle SET_ACTIVE_TILES =
+            fn("rt_set_active_tiles", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT));
+    private static final MethodHandle READ_TILE_FRAMES =
+            fn("rt_read_tile_frames", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS));
+    private static final MethodHandle WRITE_TILE_FRAMES =
+            fn("rt_write_tile_frames", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT));
+    private static final MethodHandle NOISE_FROM_TILE_SUMS_FRAMES =
+            fn("rt_noise_from_tile_sums_frames", FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, ADDRESS));
+    private static final MethodHandle ADAPTIVE_SELECT = fn("rt_adaptive_select",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_FLOAT, ADDRESS, ADDRESS));
+    private static final MethodHandle RENDER_ADAPTIVE = fn("rt_render_adaptive",
+            FunctionDescriptor.of(JAVA_INT, ADDRESS, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_INT, JAVA_LONG, JAVA_FLOAT, ADDRESS, ADDRESS));
 
     private final MemorySegment ctx;
     private int width, height;
@@ -387,6 +399,80 @@ public final class RtAmd implements AutoCloseable {
             MemorySegment st = a.allocate(NoiseStats.BYTES);
             check(call(() -> (int) RENDER_UNTIL.invokeExact(ctx, firstFrame, maxFrames, batchFrames, seed, targetNoise,
                     done, st)), ctx);
+            framesDone[0] = done.get(JAVA_INT, 0);
+            return NoiseStats.of(st);
+        }
+    }
+
+    /**
+     * rt_set_active_tiles: one byte per 8x8 tile (row-major); render() then samples only the tiles whose
+     * byte is non-zero.  null: every tile again.  One device, no partition.
+     */
+    public void setActiveTiles(byte[] active) {
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment m = active == null ? MemorySegment.NULL : a.allocateFrom(JAVA_BYTE, active);
+            int n = active == null ? 0 : active.length;
+            check(call(() -> (int) SET_ACTIVE_TILES.invokeExact(ctx, m, n)), ctx);
+        }
+    }
+
+    /** rt_read_tile_frames: the frames 1 .. n each tile holds (0 = invalid). */
+    public int[] readTileFrames() {
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment n = a.allocate(JAVA_INT);
+            check(call(() -> (int) READ_TILE_FRAMES.invokeExact(ctx, MemorySegment.NULL, 0, n)), ctx);
+            int tiles = n.get(JAVA_INT, 0);
+            MemorySegment out = a.allocate(JAVA_INT, Math.max(1, tiles));
+            check(call(() -> (int) READ_TILE_FRAMES.invokeExact(ctx, out, tiles, n)), ctx);
+            return out.asSlice(0, (long) tiles * 4).toArray(JAVA_INT);
+        }
+    }
+
+    /** rt_write_tile_frames: a checkpoint's per-tile counts (after writeCheckpoint). */
+    public void writeTileFrames(int[] frames) {
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment f = a.allocateFrom(JAVA_INT, frames);
+            check(call(() -> (int) WRITE_TILE_FRAMES.invokeExact(ctx, f, frames.length)), ctx);
+        }
+    }
+
+    /** rt_noise_from_tile_sums_frames: readTileSums records with one frame count per tile. */
+    public static NoiseStats noiseFromTileSumsFrames(int[] records, int[] frames) {
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment in = a.allocateFrom(JAVA_INT, records);
+            MemorySegment fr = a.allocateFrom(JAVA_INT, frames);
+            MemorySegment st = a.allocate(NoiseStats.BYTES);
+            int rc = call(() -> (int) NOISE_FROM_TILE_SUMS_FRAMES.invokeExact(in, fr, frames.length, st));
+            if (rc != 0) throw new IllegalArgumentException("rt_noise_from_tile_sums_frames: every count >= 2 required");
+            return NoiseStats.of(st);
+        }
+    }
+
+    /** rt_adaptive_select: which active tiles keep sampling after {@code frames} frames (active null: all). */
+    public static byte[] adaptiveSelect(int[] records, byte[] active, int frames, int minFrames, float target) {
+        try (Arena a = Arena.ofConfined()) {
+            int tiles = records.length / 4;
+            MemorySegment in = a.allocateFrom(JAVA_INT, records);
+            MemorySegment act = active == null ? MemorySegment.NULL : a.allocateFrom(JAVA_BYTE, active);
+            MemorySegment out = a.allocate(JAVA_BYTE, Math.max(1, tiles));
+            int rc = call(() -> (int) ADAPTIVE_SELECT.invokeExact(in, act, tiles, frames, minFrames, target, out,
+                    MemorySegment.NULL));
+            if (rc != 0) throw new IllegalArgumentException("rt_adaptive_select: frames >= 1, minFrames >= 2 required");
+            return out.asSlice(0, tiles).toArray(JAVA_BYTE);
+        }
+    }
+
+    /**
+     * rt_render_adaptive: renderUntil with the per-tile stopping rule; framesDone[0] = the frames of the
+     * longest-sampled tiles.  Needs setMoments(true); no mask may be set.
+     */
+    public NoiseStats renderAdaptive(int firstFrame, int maxFrames, int batchFrames, int minFrames, long seed,
+                                     float targetNoise, int[] framesDone) {
+        try (Arena a = Arena.ofConfined()) {
+            MemorySegment done = a.allocate(JAVA_INT);
+            MemorySegment st = a.allocate(NoiseStats.BYTES);
+            check(call(() -> (int) RENDER_ADAPTIVE.invokeExact(ctx, firstFrame, maxFrames, batchFrames, minFrames, seed,
+                    targetNoise, done, st)), ctx);
             framesDone[0] = done.get(JAVA_INT, 0);
             return NoiseStats.of(st);
         }

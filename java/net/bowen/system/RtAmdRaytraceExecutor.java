@@ -137,6 +137,22 @@ public class RtAmdRaytraceExecutor {
         return st;
     }
 
+    /**
+     * raytraceUntil with the per-tile stopping rule (rt_render_adaptive): a tile stops once it holds at
+     * least {@code minFrames} frames and its own noise estimate is within {@code noise}; the others go
+     * on, up to samplePerPixel frames.  numSamples counts the longest-sampled tiles' frames.
+     */
+    public RtAmd.NoiseStats raytraceAdaptive(float noise, int batch, int minFrames, long seed) {
+        int left = samplePerPixel - numSamples;
+        if (left <= 0) throw new IllegalStateException("raytraceAdaptive: samplePerPixel is the cap and it is reached");
+        if (numSamples == 0) startMillis = System.currentTimeMillis();
+        int[] done = new int[1];
+        RtAmd.NoiseStats st = rt.renderAdaptive(numSamples + 1, left, batch, minFrames, seed, noise, done);
+        numSamples += done[0];
+        if (st.converged()) samplePerPixel = numSamples;
+        return st;
+    }
+
     private int launch(int n) {
         if (n <= 0) return 0;
         if (numSamples == 0) startMillis = System.currentTimeMillis();

@@ -122,6 +122,12 @@ int validate(rt_ctx* c) {
 
 namespace {
 
+// every tile holds frames 1 .. n (0: none valid): the uniform form of the per-tile counts (rt_ctx.h)
+void set_all_frames(rt_ctx* c, int n) {
+    c->moments_frames = n;
+    c->tile_frames.clear();
+}
+
 // the links the launch walks: with the box pre-test nodes (option box_vnodes) when every box has a
 // compact record and the pre-test is on (its margin is the nodes' growth: rebuilt when it changes)
 void refresh_walk(rt_ctx* c, float box_margin) {
@@ -311,7 +317,7 @@ int rt_destroy(rt_ctx* c) {
         dev_free(d.tile_done); dev_free(d.samples); dev_free(d.wbuf); dev_free(d.dquads); dev_free(d.dboxes);
         dev_free(d.finfo); dev_free(d.f2inner); dev_free(d.f2leaves); dev_free(d.links); dev_free(d.dboxc);
         dev_free(d.gather); dev_free(d.full); dev_free(d.perlin_pk); dev_free(d.sflags);
-        dev_free(d.m2); dev_free(d.tile_sums); dev_free(d.node_hits);
+        dev_free(d.m2); dev_free(d.tile_sums); dev_free(d.node_hits); dev_free(d.tile_list);
         comm_destroy(d);
         if (d.ring) (void)hipHostFree(d.ring);
         for (auto& e : d.ring_ev)
@@ -496,6 +502,9 @@ int rt_resize(rt_ctx* c, int w, int h) {
         if (r) return r;
     }
     c->staged_frames = 0;
+    set_all_frames(c, 0);   // another image: no tile holds a frame, and a tile mask no longer fits it
+    c->mask_set = false;
+    c->act_list.clear();
     if (c->moments) return alloc_moments(c, c->devs[0]);
     return RT_OK;
 }
@@ -505,7 +514,7 @@ int rt_bind_device_image(rt_ctx* c, void* ptr, size_t nbytes) {
     if (c->devs.size() != 1) return set_err(c, RT_ERR_STATE, "device image binding needs a 1-device context");
     Device& d = c->devs[0];
     if (c->width <= 0) return set_err(c, RT_ERR_STATE, "rt_resize first");
-    c->moments_frames = 0;   // another image: its moments are not the ones held
+    set_all_frames(c, 0);   // another image: its moments are not the ones held
     if (!ptr) {
         d.image_ptr = (float*)d.image.ptr;
         d.image_bound = false;
@@ -657,15 +666,48 @@ int rt_render(rt_ctx* c, int first_frame, int n_frames, const float* rand_factor
     // restarts them (the fold zeroes them at frame 1), one from moments_frames + 1 extends them,
     // any other leaves them invalid.
     const bool mom = c->moments && n_frames > 0 && c->devs[0].local_rows > 0;   // (a rank may own no row)
-    int mom_after = c->moments_frames;
-    if (mom) {
-        if (!c->devs[0].m2.ptr) return set_err(c, RT_ERR_STATE, "sample moments: no buffer (rt_resize)");
-        const bool follows = first_frame == 1 || (c->moments_frames > 0 && first_frame == c->moments_frames + 1);
-        mom_after = follows ? first_frame - 1 + n_frames : 0;
-        c->moments_frames = 0;   // until every launch is queued
+    if (mom && !c->devs[0].m2.ptr) return set_err(c, RT_ERR_STATE, "sample moments: no buffer (rt_resize)");
+    // A tile mask (rt_set_active_tiles): the units run over the active tiles alone.
+    const bool masked = c->mask_set;
+    if (masked && c->variant != 0 && c->variant != 39)
+        return set_err(c, RT_ERR_STATE, "a tile mask runs on the default kernel structure only");
+    // The per-tile frame counts (rt_ctx.h) of the tiles this call samples: from frame 1 they restart,
+    // from their count + 1 they extend, anything else leaves them invalid; the other tiles keep theirs.
+    // A single-device context keeps them with the moments off too (the image's frames).
+    const bool track = (mom || c->devs.size() == 1) && n_frames > 0 && c->devs[0].local_rows > 0;
+    int all_after = c->moments_frames;
+    std::vector<int32_t> tiles_after;
+    if (track) {
+        auto step = [&](int cnt) {
+            return (first_frame == 1 || (cnt > 0 && first_frame == cnt + 1)) ? first_frame - 1 + n_frames : 0;
+        };
+        if (!masked && c->tile_frames.empty()) {
+            all_after = step(c->moments_frames);
+        } else {
+            const int nt = ((c->width + 7) / 8) * ((c->devs[0].local_rows + 7) / 8);
+            tiles_after = c->tile_frames;
+            if (tiles_after.empty()) tiles_after.assign((size_t)nt, c->moments_frames);
+            if (masked) {
+                for (int32_t t : c->act_list) tiles_after[(size_t)t] = step(tiles_after[(size_t)t]);
+            } else {
+                for (int32_t& v : tiles_after) v = step(v);
+            }
+            all_after = nt > 0 ? *std::min_element(tiles_after.begin(), tiles_after.end()) : 0;
+            if (nt == 0 || all_after == *std::max_element(tiles_after.begin(), tiles_after.end())) tiles_after.clear();
+        }
+        if (!masked || !c->act_list.empty()) set_all_frames(c, 0);   // until every launch is queued
     }
     for (Device& d : c->devs) {
         HIPCHK(c, hipSetDevice(d.id));
+        if (masked && c->act_list.empty()) {
+            // no tile to sample: nothing is launched or read; the events keep rt_sync / rt_last_render_ns working
+            HIPCHK(c, hipEventRecord(d.ev_start, d.stream));
+            HIPCHK(c, hipEventRecord(d.ev_stop, d.stream));
+            d.timed = true;
+            c->last_launch[RT_LI_TILES_ACTIVE] = 0;   // (the other fields keep the previous launch's)
+            c->launched = c->launched || n_frames > 0;
+            continue;
+        }
         bind_device(c, d, a);
         if (!d.args.ptr) {
             if ((r = ensure(c, d, d.counter, 256))) return r;
@@ -694,7 +736,12 @@ int rt_render(rt_ctx* c, int first_frame, int n_frames, const float* rand_factor
         const size_t n_pixels = (size_t)d.local_rows * c->width;
         size_t free_b = 0, total_b = 0;
         const size_t avail = hipMemGetInfo(&free_b, &total_b) == hipSuccess ? free_b + d.samples.bytes : SIZE_MAX;
-        const Split split = plan_split(n_tiles, waves, n_frames, c->chunk_target, c->staged_chunk_target, c->stage_tiles,
+        // under a mask the split counts the active tiles, so a sparse one is still cut into enough units
+        // per resident wave; staging stays indexed by pixel (its layout and size do not change)
+        const int n_act = masked ? (int)c->act_list.size() : n_tiles;
+        a.tile_list = masked ? (const int*)d.tile_list.ptr : nullptr;
+        a.n_active = n_act;
+        const Split split = plan_split(n_act, waves, n_frames, c->chunk_target, c->staged_chunk_target, c->stage_tiles,
                                        mom, n_pixels, c->sample_budget, avail);
         const int per_launch = split.per_launch, chunks_wanted = split.chunks_wanted;
         const bool staged = split.staged;
@@ -754,7 +801,10 @@ int rt_render(rt_ctx* c, int first_frame, int n_frames, const float* rand_factor
         d.timed = true;
         c->launched = c->launched || n_frames > 0;
     }
-    if (mom) c->moments_frames = mom_after;
+    if (track) {
+        c->moments_frames = all_after;
+        c->tile_frames.swap(tiles_after);
+    }
     return RT_OK;
 }
 
@@ -846,7 +896,7 @@ int rt_write_image(rt_ctx* c, const float* rgba) {
     if (c->width <= 0) return set_err(c, RT_ERR_STATE, "no image");
     int r = rt_sync(c);
     if (r) return r;
-    c->moments_frames = 0;   // rt_write_moments restores them from the same checkpoint
+    set_all_frames(c, 0);   // rt_write_moments restores them from the same checkpoint
     for (Device& d : c->devs) {
         HIPCHK(c, hipSetDevice(d.id));
         std::vector<float> local((size_t)d.local_rows * c->width * 4);
@@ -879,12 +929,12 @@ int rt_set_moments(rt_ctx* c, int on) {
         dev_free(d.m2);
         dev_free(d.tile_sums);
         c->moments = false;
-        c->moments_frames = 0;
+        set_all_frames(c, 0);
         return RT_OK;
     }
     if (c->moments) return RT_OK;
     c->moments = true;
-    c->moments_frames = 0;
+    set_all_frames(c, 0);
     return c->width > 0 ? alloc_moments(c, d) : RT_OK;
 }
 
@@ -915,10 +965,10 @@ int rt_write_moments(rt_ctx* c, const float* m2_rgba, int n_frames) {
     if (r) return r;
     Device& d = c->devs[0];
     HIPCHK(c, hipSetDevice(d.id));
-    c->moments_frames = 0;
+    set_all_frames(c, 0);
     r = h2d(c, d, d.m2.ptr, m2_rgba, (size_t)d.local_rows * c->width * 16);
     if (r) return r;
-    c->moments_frames = n_frames;
+    set_all_frames(c, n_frames);
     return RT_OK;
 }
 
@@ -953,7 +1003,138 @@ int rt_noise(rt_ctx* c, rt_noise_stats* out) {
     std::vector<rt_tile_sum> tiles((size_t)n);
     r = rt_read_tile_sums(c, tiles.data(), n, &n);
     if (r) return r;
+    if (!c->tile_frames.empty())   // the tiles hold different counts (a tile mask): each with its own
+        return rt_noise_from_tile_sums_frames(tiles.data(), c->tile_frames.data(), n, out);
     return rt_noise_from_tile_sums(tiles.data(), n, c->moments_frames, out);
+}
+
+// ---- tile masks, per-tile frame counts and the adaptive loop (rt.h) ----
+
+namespace {
+int tiles_ready(rt_ctx* c, const char* what) {
+    if (c->devs.size() != 1) return set_err(c, RT_ERR_STATE, std::string(what) + " needs a 1-device context");
+    if (c->proc_world > 1) return set_err(c, RT_ERR_STATE, std::string(what) + ": not under rt_set_partition");
+    if (c->width <= 0) return set_err(c, RT_ERR_STATE, "no image");
+    return RT_OK;
+}
+int tile_count(const rt_ctx* c) { return ((c->width + 7) / 8) * ((c->devs[0].local_rows + 7) / 8); }
+}  // namespace
+
+int rt_set_active_tiles(rt_ctx* c, const uint8_t* active, int n_tiles) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    int r = tiles_ready(c, "rt_set_active_tiles");
+    if (r) return r;
+    if (!active) {
+        c->mask_set = false;
+        c->act_list.clear();
+        return RT_OK;
+    }
+    const int nt = tile_count(c);
+    if (n_tiles != nt) return set_err(c, RT_ERR_INVALID_ARG, "rt_set_active_tiles: n_tiles does not match the image");
+    std::vector<int32_t> list;
+    for (int t = 0; t < nt; t++)
+        if (active[t]) list.push_back(t);
+    Device& d = c->devs[0];
+    HIPCHK(c, hipSetDevice(d.id));
+    if (!list.empty()) {
+        // ordered on the render stream and complete on return: a queued launch keeps the list it was given
+        HIPCHK(c, hipStreamSynchronize(d.stream));
+        if ((r = ensure(c, d, d.tile_list, (size_t)nt * sizeof(int32_t)))) return r;
+        if ((r = h2d(c, d, d.tile_list.ptr, list.data(), list.size() * sizeof(int32_t)))) return r;
+    }
+    c->act_list.swap(list);
+    c->mask_set = true;
+    return RT_OK;
+}
+
+int rt_read_tile_frames(rt_ctx* c, int32_t* frames, int cap, int* n_tiles) {
+    if (!c || !n_tiles) return RT_ERR_INVALID_ARG;
+    int r = tiles_ready(c, "rt_read_tile_frames");
+    if (r) return r;
+    const int nt = tile_count(c);
+    *n_tiles = nt;
+    if (!frames) return RT_OK;
+    if (cap < nt) return set_err(c, RT_ERR_LIMIT, "rt_read_tile_frames: frames is too small");
+    for (int t = 0; t < nt; t++) frames[t] = c->tile_frames.empty() ? c->moments_frames : c->tile_frames[(size_t)t];
+    return RT_OK;
+}
+
+int rt_write_tile_frames(rt_ctx* c, const int32_t* frames, int n_tiles) {
+    if (!c || !frames) return RT_ERR_INVALID_ARG;
+    int r = tiles_ready(c, "rt_write_tile_frames");
+    if (r) return r;
+    const int nt = tile_count(c);
+    if (n_tiles != nt) return set_err(c, RT_ERR_INVALID_ARG, "rt_write_tile_frames: n_tiles does not match the image");
+    for (int t = 0; t < nt; t++)
+        if (frames[t] < 0) return set_err(c, RT_ERR_INVALID_ARG, "rt_write_tile_frames: a count is negative");
+    if (nt == 0) return RT_OK;
+    const int lo = *std::min_element(frames, frames + nt), hi = *std::max_element(frames, frames + nt);
+    set_all_frames(c, lo);
+    if (lo != hi) c->tile_frames.assign(frames, frames + nt);
+    return RT_OK;
+}
+
+int rt_render_adaptive(rt_ctx* c, int first_frame, int max_frames, int batch_frames, int min_frames, uint64_t seed,
+                       float target_noise, int* frames_done, rt_noise_stats* last) {
+    if (!c || !frames_done || !last) return RT_ERR_INVALID_ARG;
+    *frames_done = 0;
+    std::memset(last, 0, sizeof(*last));
+    if (first_frame < 1 || max_frames < 1 || batch_frames < 1 || min_frames < 2 || first_frame > INT_MAX - max_frames)
+        return set_err(c, RT_ERR_INVALID_ARG, "first_frame >= 1, max_frames >= 1, batch_frames >= 1, min_frames >= 2");
+    int r = tiles_ready(c, "rt_render_adaptive");
+    if (r) return r;
+    if (!c->moments) return set_err(c, RT_ERR_STATE, "rt_set_moments(ctx, 1) first");
+    if (c->mask_set) return set_err(c, RT_ERR_STATE, "rt_render_adaptive: a tile mask is set (rt_set_active_tiles(ctx, NULL, 0))");
+    const int nt = tile_count(c);
+    // the tiles still sampled: all of them from frame 1; on a resume the ones at the largest count
+    std::vector<uint8_t> active((size_t)nt, 1), next((size_t)nt, 0);
+    int n_active = nt;
+    if (first_frame != 1) {
+        int hi = c->moments_frames;
+        for (int32_t v : c->tile_frames) hi = std::max(hi, (int)v);
+        if (c->moments_frames < 1 || first_frame != hi + 1)
+            return set_err(c, RT_ERR_STATE, "rt_render_adaptive: first_frame is 1, or the largest tile count + 1 of valid counts");
+        if (!c->tile_frames.empty()) {
+            n_active = 0;
+            for (int t = 0; t < nt; t++) n_active += active[(size_t)t] = c->tile_frames[(size_t)t] == hi;
+        }
+    }
+    std::vector<float> rf((size_t)std::min(batch_frames, max_frames));
+    std::vector<rt_tile_sum> tiles((size_t)nt);
+    int done = 0, converged = 0;
+    while (done < max_frames) {
+        const int n = std::min(batch_frames, max_frames - done);
+        for (int i = 0; i < n; i++) rf[i] = rt_frame_rand_factor(seed, (uint64_t)(first_frame + done + i - 1));
+        // (every tile active: the plain launch, the same bits)
+        r = n_active == nt ? rt_set_active_tiles(c, nullptr, 0) : rt_set_active_tiles(c, active.data(), nt);
+        if (!r) r = rt_render(c, first_frame + done, n, rf.data());
+        if (!r) r = rt_sync(c);   // not pipelined: the selection depends on the inputs alone
+        if (r) break;
+        done += n;
+        *frames_done = done;
+        const int F = first_frame + done - 1;   // the frames every active tile holds
+        if (F < 2) continue;   // one frame: no variance yet
+        int m = 0;
+        r = rt_read_tile_sums(c, tiles.data(), nt, &m);
+        if (!r) r = rt_adaptive_select(tiles.data(), active.data(), nt, F, min_frames, target_noise, next.data(), &n_active);
+        if (r) break;
+        active.swap(next);
+        if (n_active == 0) {
+            converged = 1;
+            break;
+        }
+    }
+    const int r2 = rt_set_active_tiles(c, nullptr, 0);   // no mask is left set
+    if (r) return r;
+    if (r2) return r2;
+    if (c->moments_frames < 2) {
+        last->frames = c->moments_frames;
+        last->noise = (double)INFINITY;
+    } else if ((r = rt_noise(c, last))) {
+        return r;
+    }
+    last->converged = converged;
+    return RT_OK;
 }
 
 int rt_render_until(rt_ctx* c, int first_frame, int max_frames, int batch_frames, uint64_t seed, float target_noise,

@@ -45,6 +45,7 @@ struct Device {
     DevBuf sflags;           // sparse staging: per staged sample, 1 where its colour was stored
     DevBuf m2;               // rt_set_moments: per-pixel float4 second moments [local_rows][W] (rt_moments.hip)
     DevBuf tile_sums;        // ... and their per-tile sums (rt_read_tile_sums)
+    DevBuf tile_list;        // rt_set_active_tiles: the active tiles' indices, ascending (int32)
     DevBuf wbuf;             // pooled units (ordered / one chunk): per resident wave 64 x chunk_frames colours
     DevBuf finfo;            // exact near-first walk tables (variant 61)
     DevBuf f2inner, f2leaves;
@@ -181,6 +182,16 @@ struct rt_ctx {
     // invalid (nothing rendered yet, a first_frame gap, the image overwritten or resized).
     bool moments = false;
     int moments_frames = 0;
+    // Per-tile frame counts (rt_read_tile_frames): the frames 1 .. n each 8x8 tile of the first device's
+    // image holds, 0 = invalid.  While every tile holds the same count tile_frames is empty and
+    // moments_frames is that count; once they differ (a launch under a tile mask) tile_frames holds
+    // one count per tile and moments_frames their minimum, so "valid" stays moments_frames >= 1.
+    // Single-device contexts keep them whether or not the moments are on.
+    std::vector<int32_t> tile_frames;
+    // rt_set_active_tiles: the mask in effect (mask_set), its tiles' indices in ascending order
+    // (Device::tile_list holds the same on the device)
+    bool mask_set = false;
+    std::vector<int32_t> act_list;
     // the first device's staged colours of the last launch (rt_debug_read_samples): frames, sparse flags
     int staged_frames = 0;
     bool staged_sparse = false;
@@ -266,6 +277,7 @@ inline int alloc_moments(rt_ctx* c, Device& d) {
     HIPCHK(c, hipSetDevice(d.id));
     HIPCHK(c, hipStreamSynchronize(d.stream));
     c->moments_frames = 0;
+    c->tile_frames.clear();
     dev_free(d.m2);
     dev_free(d.tile_sums);
     const size_t bytes = (size_t)d.local_rows * c->width * 16;

@@ -42,6 +42,61 @@ int rt_noise_from_tile_sums(const rt_tile_sum* tiles, int n_tiles, int frames, r
     return RT_OK;
 }
 
+int rt_noise_from_tile_sums_frames(const rt_tile_sum* tiles, const int32_t* frames, int n_tiles, rt_noise_stats* out) {
+    if (!out || n_tiles < 0 || (n_tiles > 0 && (!tiles || !frames))) return RT_ERR_INVALID_ARG;
+    for (int i = 0; i < n_tiles; i++)
+        if (frames[i] < 2) return RT_ERR_INVALID_ARG;
+    rt_noise_stats s;
+    std::memset(&s, 0, sizeof(s));
+    double var = 0.0;   // sum over tiles of m2y_t / (n_t (n_t - 1)), in tile order
+    for (int i = 0; i < n_tiles; i++) {
+        const double n = (double)frames[i];
+        var += (double)tiles[i].m2y / (n * (n - 1.0));
+        s.sum_m2y += (double)tiles[i].m2y;
+        s.sum_y += (double)tiles[i].y;
+        s.pixels += tiles[i].pixels;
+        s.bad += tiles[i].bad;
+        s.frames = std::max(s.frames, (int)frames[i]);
+    }
+    const double p = (double)(s.pixels - s.bad);
+    const double num = std::sqrt(std::max(0.0, var) * p);
+    if (s.sum_y == 0.0) s.noise = num == 0.0 ? 0.0 : (double)INFINITY;
+    else s.noise = num / s.sum_y;
+    *out = s;
+    return RT_OK;
+}
+
+int rt_adaptive_select(const rt_tile_sum* tiles, const uint8_t* active_in, int n_tiles, int frames, int min_frames,
+                       float target, uint8_t* active_out, int* n_active) {
+    if (n_tiles < 0 || (n_tiles > 0 && (!tiles || !active_out)) || frames < 1 || min_frames < 2)
+        return RT_ERR_INVALID_ARG;
+    double sy = 0.0, sp = 0.0;   // over all tiles, stopped ones included, in tile order
+    for (int i = 0; i < n_tiles; i++) {
+        sy += (double)tiles[i].y;
+        sp += (double)(tiles[i].pixels - tiles[i].bad);
+    }
+    const double ybar = sp > 0.0 ? sy / sp : 0.0;
+    const double lim = (double)target * ybar;
+    const double F = (double)frames;
+    int n = 0;
+    for (int i = 0; i < n_tiles; i++) {
+        bool keep = !active_in || active_in[i] != 0;
+        if (keep && frames >= min_frames) {
+            const double pt = (double)(tiles[i].pixels - tiles[i].bad);
+            if (pt == 0.0) {
+                keep = false;
+            } else {
+                const double v = (double)tiles[i].m2y / (F * (F - 1.0)) / pt;
+                keep = !(v <= lim * lim);
+            }
+        }
+        active_out[i] = keep ? 1 : 0;
+        n += keep;
+    }
+    if (n_active) *n_active = n;
+    return RT_OK;
+}
+
 int rt_deinterleave_rows(const float* gathered, int width, int height, int world, int stripe_rows, float* out) {
     if (!gathered || !out || width <= 0 || height <= 0 || world < 1 || stripe_rows < 1) return RT_ERR_INVALID_ARG;
     int padded = padded_rows_of(height, world, stripe_rows);

@@ -127,7 +127,11 @@ struct rt_kernel_args {
     // staged launches may end with tail_chunks chunks of one frame each (option tail_chunks): chunk
     // c >= n_chunks - tail_chunks holds frame n_frames - (n_chunks - c)
     int n_chunks, chunk_frames, tail_chunks;
-    unsigned* tile_done;         // ordered chunks: per tile, the chunks published so far (zeroed per launch)
+    // the tiles the launch samples (rt_set_active_tiles): n_active of them, tile_list their indices in
+    // ascending order, and unit = chunk * n_active + place in tile_list; no mask: nullptr and every tile
+    const int* tile_list;
+    int n_active;
+    unsigned* tile_done;        // ordered chunks: per tile, the chunks published so far (zeroed per launch)
     float4* samples;             // staged chunks: per-frame colours [n_frames][n_pixels]; nullptr = ordered / one chunk
     uint8_t* sflags;             // sparse staging (render_stream): per sample [n_frames][n_pixels] 1 when its colour
                                  // is not (+0, +0, +0) and was stored in `samples`, else 0; nullptr = dense
@@ -213,7 +217,7 @@ struct rt_kernel_args {
 
 // What rt_launch_render launched (rt_debug_last_launch)
 enum { RT_LI_SHAPE = 0, RT_LI_BLOCK, RT_LI_FASTDIV, RT_LI_PRETEST, RT_LI_LDS, RT_LI_LDS_NODES, RT_LI_COMPACT,
-       RT_LI_STAGED, RT_LI_CHUNKS, RT_LI_SPINE, RT_LI_SPARSE, RT_LI_SPAIR, RT_LI_LEAF_PF, RT_LI_SHADE_LDS, RT_LI_WALK_FRAC, RT_LI_BVH_MODE, RT_LI_VNODES, RT_LI_COLLAPSED, RT_LI_REBUILT, RT_LI_BOXQ, RT_LI_N = 20 };
+       RT_LI_STAGED, RT_LI_CHUNKS, RT_LI_SPINE, RT_LI_SPARSE, RT_LI_SPAIR, RT_LI_LEAF_PF, RT_LI_SHADE_LDS, RT_LI_WALK_FRAC, RT_LI_BVH_MODE, RT_LI_VNODES, RT_LI_COLLAPSED, RT_LI_REBUILT, RT_LI_BOXQ, RT_LI_TILES_ACTIVE, RT_LI_N = 21 };
 
 #ifdef RT_AB_KNOBS
 // A/B library only (rt_kernel_variants.hip): the structures the release library does not ship
@@ -230,6 +234,9 @@ int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int
 // launchers implemented in rt_moments.hip
 // a staged launch's colours (a.samples, a.sflags) folded into a.image and moments [n_pixels] float4
 int rt_launch_fold_moments(const rt_kernel_args& a, void* moments, void* stream);
+// the same under a tile mask (a.tile_list, a.n_active): one wave per active tile, only its pixels' words
+// are read or written; moments may be NULL (the mean alone, fold_kernel's operations)
+int rt_launch_fold_tiles(const rt_kernel_args& a, void* moments, void* stream);
 // image, moments [local_rows][width] float4 -> out: one rt_tile_sum per 8x8 tile, row-major
 int rt_launch_tile_sums(const void* image, const void* moments, int width, int local_rows, void* out, void* stream);
 // Row y of the image in the gathered stripe blocks [world][padded_rows][W]: rank k = s % world

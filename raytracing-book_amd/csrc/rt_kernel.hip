@@ -57,14 +57,22 @@ namespace {
 // straight to P.samples and need no slots.  A lane's sample is its pixel (fx, fy),
 // its slot `up` and its colour's place `dst` (slot offset frame-in-chunk * 64 +
 // pixel slot, or the staged index).
+// A launch under a tile mask (rt_set_active_tiles) runs the RT_OPT_MASK twin of its kernel (MASK): its
+// units are over the active tiles alone, n_tiles is their count P.n_active and P.tile_list their
+// indices, ascending (one scalar load per unit; the host's copy is complete before the launch and no
+// kernel writes it).  Everything after the lookup works from the tile's real index.  (A run-time test
+// of P.tile_list in the one kernel kept every instance's registers but cost scene 6 +0.5% without a
+// mask, profiles/adaptive_cost_runtime_test.json; the kernels without the bit compile as before.)
 struct UnitGeo {
     int chunk, tile, tx0, ly0, wt, ht, f0, f1;
     uint32_t total;
 };
+template <bool MASK>
 __device__ __forceinline__ UnitGeo unit_geo(const KP& P, int u, int n_tiles, int tiles_x) {
     UnitGeo g;
     g.chunk = u / n_tiles;
     g.tile = u - g.chunk * n_tiles;
+    if (MASK) g.tile = ldc_i(P.tile_list + g.tile);
     g.tx0 = (g.tile % tiles_x) * 8;
     g.ly0 = (g.tile / tiles_x) * 8;
     g.wt = min(8, P.width - g.tx0);
@@ -109,7 +117,8 @@ __device__ __forceinline__ void render_stream(const KP& P, const float4* __restr
     const bool staged = STD || P.samples != nullptr;
     const bool sparse = STD || P.sflags != nullptr;   // (staged launches)
     const int tiles_x = (P.width + 7) >> 3;
-    const int n_tiles = tiles_x * ((P.local_rows + 7) >> 3);
+    constexpr bool MASK = (OPT & RT_OPT_MASK) != 0;
+    const int n_tiles = MASK ? P.n_active : tiles_x * ((P.local_rows + 7) >> 3);   // the tiles the launch samples
     const int n_units = n_tiles * P.n_chunks;
     const uint32_t slot_f4 = 64u * (uint32_t)P.chunk_frames;
     float4* const wbase = staged ? nullptr : P.wbuf + (size_t)gwave * 2 * slot_f4;
@@ -132,7 +141,7 @@ __device__ __forceinline__ void render_stream(const KP& P, const float4* __restr
     int cur = 1;
     uint32_t next = 0, total_cur = 0;
     bool no_more = false;
-    UnitGeo gc = unit_geo(P, 0, n_tiles, tiles_x);   // the pool unit's geometry
+    UnitGeo gc = unit_geo<MASK>(P, 0, n_tiles, tiles_x);   // the pool unit's geometry
     // per lane
     int up = 0;
     uint32_t dst = 0;
@@ -183,7 +192,7 @@ __device__ __forceinline__ void render_stream(const KP& P, const float4* __restr
                 const bool l0 = unit0 >= 0, l1 = unit1 >= 0;
                 if (!l0 && !l1) break;
                 const int p = (l0 && (!l1 || unit0 < unit1)) ? 0 : 1;
-                const UnitGeo g = unit_geo(P, p ? unit1 : unit0, n_tiles, tiles_x);
+                const UnitGeo g = unit_geo<MASK>(P, p ? unit1 : unit0, n_tiles, tiles_x);
                 if ((p == cur && next < g.total) || (p ? done1 : done0) < g.total) break;
                 // all of the unit's colours are in slot p: fold them per pixel in frame order
                 __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
@@ -244,7 +253,7 @@ __device__ __forceinline__ void render_stream(const KP& P, const float4* __restr
                     else unit0 = u;
                 }
                 cur = o;
-                gc = unit_geo(P, u, n_tiles, tiles_x);
+                gc = unit_geo<MASK>(P, u, n_tiles, tiles_x);
                 total_cur = gc.total;
                 next = 0;
                 continue;
@@ -568,6 +577,7 @@ int rt_resident_waves(void) {
 
 int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int* info, void* moments) {
     if (a.local_rows <= 0 || a.width <= 0 || a.n_frames <= 0) return 0;
+    if (a.n_active <= 0) return -1;   // the units divide by it (unit_geo); the caller skips an empty mask
     hipStream_t st = (hipStream_t)stream;
     // The release library has one kernel structure (tests/test_gpu_*.py pin it to the oracle):
     // pooled samples streamed over units with walks and shading in batches (render_stream) over
@@ -631,6 +641,7 @@ int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int
                              ((a.sph_pairs && !a.box_all_cmp) || (a.sph_pairs == 2 && a.fastdiv))) ? 1 : 0;
         info[RT_LI_LEAF_PF] = (pool && (shape == LINK_LDS || shape == LINK_TL)) ? a.leaf_pf : 0;
         info[RT_LI_WALK_FRAC] = a.walk_frac;
+        info[RT_LI_TILES_ACTIVE] = a.n_active;
         info[RT_LI_SHADE_LDS] = (a.sph_mat_lds >= 0) + 2 * (a.box_mat_lds >= 0) + 4 * (a.tex_lds >= 0);
     }
     // Arguments live in device memory: the by-value kernarg struct would be copied
@@ -649,12 +660,14 @@ int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int
     constexpr int SM = RT_OPT_POOL | RT_OPT_SM | RT_OPT_STREAM;
     // the instantiations: <MINW, STATS, BLOCK, OPT> (stats twins in the A/B build only)
 #ifdef RT_AB_KNOBS
-#define RT_KERNEL(BLOCK, OPT)                                                                            \
+#define RT_KERNEL1(BLOCK, OPT)                                                                           \
     (stats ? launch_persistent(render_persistent<4, true, BLOCK, (OPT) & ~RT_OPT_BOXQ>, BLOCK, lds, a, d, st)  \
            : launch_persistent(render_persistent<4, false, BLOCK, OPT>, BLOCK, lds, a, d, st))
 #else
-#define RT_KERNEL(BLOCK, OPT) launch_persistent(render_persistent<4, false, BLOCK, OPT>, BLOCK, lds, a, d, st)
+#define RT_KERNEL1(BLOCK, OPT) launch_persistent(render_persistent<4, false, BLOCK, OPT>, BLOCK, lds, a, d, st)
 #endif
+    // ... each with its twin for a launch under a tile mask (RT_OPT_MASK)
+#define RT_KERNEL(BLOCK, OPT) (a.tile_list ? RT_KERNEL1(BLOCK, (OPT) | RT_OPT_MASK) : RT_KERNEL1(BLOCK, OPT))
     int rc = -1;
     // the default launch's configuration (RT_OPT_STD) holds: the kernels with it compiled in
     const bool std_cfg = a.samples && a.sflags && a.media_sph &&
@@ -703,10 +716,13 @@ int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int
         default: break;
     }
 #undef RT_KERNEL
+#undef RT_KERNEL1
 #undef RT_LINK4
 #undef RT_LINK4S
     if (rc) return rc;
-    if (a.samples && moments) {   // ... and the second moments (rt_moments.hip), the same mean
+    if (a.samples && a.tile_list) {   // under a tile mask: the same folds over the active tiles' pixels alone
+        if (rt_launch_fold_tiles(a, moments, stream)) return -1;
+    } else if (a.samples && moments) {   // ... and the second moments (rt_moments.hip), the same mean
         if (rt_launch_fold_moments(a, moments, stream)) return -1;
     } else if (a.samples) {   // staged chunks: the running mean over the launch's frames
         const unsigned blocks = (unsigned)((a.n_pixels + 255) / 256);

@@ -36,6 +36,8 @@ typedef rt_kernel_args KP;
 #define RT_OPT_SPAIR 64 // with RT_OPT_STREAM: leaves of two spheres tested at once (leaf_prims_t; most leaves are)
 #define RT_OPT_BOXQ 256 // with RT_OPT_FD, RT_OPT_BOXC and RT_OPT_STD: the compact box test with one reciprocal per
                         // axis and no division per face (box_test_compact_q; option box_interior)
+#define RT_OPT_MASK 512 // with RT_OPT_STREAM: the units run over the active tiles of a tile mask (P.tile_list, P.n_active;
+                        // rt_kernel.hip unit_geo); without it the code is the unmasked kernel's, unchanged
 #define RT_OPT_STD 128  // the default launch's configuration, compiled in (rt_launch_render std_config takes these
                         // kernels when it holds): staged chunks with sparse staging (P.samples, P.sflags), every
                         // medium bounded by a sphere (P.media_sph; no out-of-line boundary call), the leaf and

@@ -2,7 +2,7 @@
 // (rt.h rt_set_moments / rt_noise).  Nothing here touches the render kernels: a staged launch's
 // colours are folded by fold_moments_kernel instead of rt_kernel.hip's fold_kernel, with the
 // same operations on the mean (so the same image bits) plus a Welford update of the second
-// moment; tile_sums_kernel reduces image and moments to one record per 8x8 tile in a fixed
+// moment (fold_tiles_kernel: either fold over the active tiles of a masked launch); tile_sums_kernel reduces image and moments to one record per 8x8 tile in a fixed
 // order, so the host's noise figure depends on the inputs alone.  All arithmetic is f32 without
 // contraction (-ffp-contract=off), and tests/test_gpu_moments.py restates it in numpy bit for bit.
 #include <hip/hip_runtime.h>
@@ -74,6 +74,73 @@ __global__ void __launch_bounds__(256) fold_moments_kernel(float4* __restrict__ 
     moments[pix] = m2;
 }
 
+// One frame of the running mean alone: fold_kernel's operations (moment_step's on the mean).
+__device__ __forceinline__ void mean_step(float4& mean, const float4 c, const int fc) {
+    const float n1 = (float)(fc - 1), n = (float)fc;
+    mean.x = (mean.x * n1 + c.x) / n;
+    mean.y = (mean.y * n1 + c.y) / n;
+    mean.z = (mean.z * n1 + c.z) / n;
+    mean.w = 1.0f;
+}
+
+// The folds of a launch under a tile mask (rt_set_active_tiles): one wave per active tile, lane
+// ty * 8 + tx its pixel, lanes outside the image idle; a pixel of any other tile is neither read
+// nor written.  Per pixel and in frame order the operations are fold_moments_kernel's (MOM) or
+// fold_kernel's, with the sparse flags read the same way, so an active pixel's image and M2
+// bits are those of the plain folds.
+template <bool MOM>
+__global__ void __launch_bounds__(256) fold_tiles_kernel(float4* __restrict__ image, float4* __restrict__ moments,
+                                                         const float4* __restrict__ samples,
+                                                         const uint8_t* __restrict__ sflags, size_t n_pixels,
+                                                         int first_frame, int n_frames,
+                                                         const int* __restrict__ tile_list, int n_active, int width,
+                                                         int local_rows) {
+    const int lane = threadIdx.x & 63;
+    const int k = (int)blockIdx.x * 4 + ((int)threadIdx.x >> 6);   // wave-uniform
+    if (k >= n_active) return;
+    const int tile = tile_list[k];
+    const int tiles_x = (width + 7) >> 3;
+    const int x = (tile % tiles_x) * 8 + (lane & 7);
+    const int y = (tile / tiles_x) * 8 + (lane >> 3);
+    if (x >= width || y >= local_rows) return;
+    const size_t pix = (size_t)y * width + x;
+    float4 mean = image[pix];
+    float4 m2 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (MOM) m2 = moments[pix];
+    const float4* s = samples + pix;
+    const float4 z4 = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+    if (sflags) {
+        const uint8_t* fl = sflags + pix;
+        int f = 0;
+        for (; f + 8 <= n_frames; f += 8) {
+            uint32_t fb[8];
+            float4 cur[8];
+#pragma unroll
+            for (int j = 0; j < 8; j++) fb[j] = fl[(size_t)(f + j) * n_pixels];
+#pragma unroll
+            for (int j = 0; j < 8; j++) cur[j] = fb[j] ? s[(size_t)(f + j) * n_pixels] : z4;
+#pragma unroll
+            for (int j = 0; j < 8; j++) {
+                if (MOM) moment_step(mean, m2, cur[j], first_frame + f + j);
+                else mean_step(mean, cur[j], first_frame + f + j);
+            }
+        }
+        for (; f < n_frames; f++) {
+            const float4 cur = fl[(size_t)f * n_pixels] ? s[(size_t)f * n_pixels] : z4;
+            if (MOM) moment_step(mean, m2, cur, first_frame + f);
+            else mean_step(mean, cur, first_frame + f);
+        }
+    } else {
+        for (int f = 0; f < n_frames; f++) {
+            const float4 cur = s[(size_t)f * n_pixels];
+            if (MOM) moment_step(mean, m2, cur, first_frame + f);
+            else mean_step(mean, cur, first_frame + f);
+        }
+    }
+    image[pix] = mean;
+    if (MOM) moments[pix] = m2;
+}
+
 __device__ __forceinline__ bool finite_f(float v) { return fabsf(v) <= __FLT_MAX__; }
 
 // One wave per 8x8 tile (row-major tiles, the render kernels' unit_geo tiles): lane ty * 8 + tx
@@ -129,6 +196,20 @@ int rt_launch_fold_moments(const rt_kernel_args& a, void* moments, void* stream)
     hipLaunchKernelGGL(fold_moments_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream,
                        reinterpret_cast<float4*>(a.image), (float4*)moments, (const float4*)a.samples,
                        (const uint8_t*)a.sflags, a.n_pixels, a.first_frame, a.n_frames);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+int rt_launch_fold_tiles(const rt_kernel_args& a, void* moments, void* stream) {
+    if (!a.samples || !a.tile_list || a.n_active <= 0 || a.n_pixels == 0 || a.n_frames <= 0) return -1;
+    const dim3 grid((unsigned)((a.n_active + 3) / 4)), block(256);
+    if (moments)
+        hipLaunchKernelGGL(fold_tiles_kernel<true>, grid, block, 0, (hipStream_t)stream, reinterpret_cast<float4*>(a.image),
+                           (float4*)moments, (const float4*)a.samples, (const uint8_t*)a.sflags, a.n_pixels,
+                           a.first_frame, a.n_frames, a.tile_list, a.n_active, a.width, a.local_rows);
+    else
+        hipLaunchKernelGGL(fold_tiles_kernel<false>, grid, block, 0, (hipStream_t)stream, reinterpret_cast<float4*>(a.image),
+                           (float4*)nullptr, (const float4*)a.samples, (const uint8_t*)a.sflags, a.n_pixels,
+                           a.first_frame, a.n_frames, a.tile_list, a.n_active, a.width, a.local_rows);
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

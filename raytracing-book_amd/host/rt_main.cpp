@@ -30,6 +30,9 @@
 // Noise target: --noise <x> renders batches of --frames-per-launch frames until the image's
 // estimated relative noise (rt_render_until: per-pixel sample moments, rt.h) is at most x, with
 // -spp as the cap, and prints "Noise target: <frames> frames, noise <value> (...)".  One device.
+// With --adaptive the target holds per 8x8 tile (rt_render_adaptive): a tile stops once it has
+// --min-frames frames (default 16) and its own estimate is within the target, the others go on; it
+// prints "Adaptive: <max frames> frames, <samples> of <W*H*max frames> samples, noise <value> (...)".
 #include "rt/rt.h"
 #include "rt/rt_scene.h"
 
@@ -55,7 +58,7 @@ struct Opt {
 };
 
 // commons-cli Options in Main.getOptions order (Main.java:43-70)
-enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_N };
+enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_N };
 const Opt kOpts[O_N] = {
     {"h", "help", false, "print help message"},
     {"s", "scene", true, "scene ID"},
@@ -70,6 +73,8 @@ const Opt kOpts[O_N] = {
     {nullptr, "preview", true, "progressive preview PNG, rewritten every --preview-every frames"},
     {nullptr, "preview-every", true, "frames between preview updates (default: --frames-per-launch)"},
     {nullptr, "noise", true, "stop once the estimated relative noise is at most this (-spp is the cap)"},
+    {nullptr, "adaptive", false, "with --noise: stop sampling each 8x8 tile once it meets the target"},
+    {nullptr, "min-frames", true, "with --adaptive: frames every tile gets before it may stop (default 16)"},
 };
 
 // HelpFormatter.printHelp("OpenGL Ray Tracer", options): options sorted by key.
@@ -231,6 +236,10 @@ int main(int argc, char** argv) {
         if (!preview.empty()) die("rtrender", "--noise and --preview do not combine");
         if (spp <= 0) die("rtrender", "--noise needs -spp >= 1 (the cap)");
     }
+    if (seen[O_ADAPTIVE] && !seen[O_NOISE]) die("rtrender", "--adaptive needs --noise <x> (the target)");
+    if (seen[O_MIN_FRAMES] && !seen[O_ADAPTIVE]) die("rtrender", "--min-frames goes with --adaptive");
+    const int min_frames = seen[O_MIN_FRAMES] ? parse_int(val[O_MIN_FRAMES]) : 16;
+    if (min_frames < 2) die("rtrender", "--min-frames must be at least 2");
 
     rts_scene* scene = nullptr;
     if (rts_build(scene_id, width, height, (uint64_t)seed, nullptr, &scene) != 0) die("rts_build", rts_last_error());
@@ -273,9 +282,26 @@ int main(int argc, char** argv) {
         rt_noise_stats st;
         int frames = 0;
         chk(rt_set_moments(ctx, 1), "rt_set_moments");
-        chk(rt_render_until(ctx, 1, spp, per_launch, (uint64_t)seed, noise_target, &frames, &st), "rt_render_until");
-        std::printf("Noise target: %d frames, noise %.6g (%s)\n", frames, st.noise,
-                    st.converged ? "converged" : "sample cap reached");
+        if (seen[O_ADAPTIVE]) {
+            chk(rt_render_adaptive(ctx, 1, spp, per_launch, min_frames, (uint64_t)seed, noise_target, &frames, &st),
+                "rt_render_adaptive");
+            // the samples taken: per tile its pixels x the frames it holds
+            int n_tiles = 0;
+            chk(rt_read_tile_frames(ctx, nullptr, 0, &n_tiles), "rt_read_tile_frames");
+            std::vector<int32_t> counts((size_t)n_tiles);
+            chk(rt_read_tile_frames(ctx, counts.data(), n_tiles, &n_tiles), "rt_read_tile_frames");
+            const int tiles_x = (width + 7) / 8;
+            long long samples = 0;
+            for (int t = 0; t < n_tiles; t++)
+                samples += (long long)std::min(8, width - (t % tiles_x) * 8) * std::min(8, height - (t / tiles_x) * 8) *
+                           counts[(size_t)t];
+            std::printf("Adaptive: %d frames, %lld of %lld samples, noise %.6g (%s)\n", frames, samples,
+                        (long long)width * height * frames, st.noise, st.converged ? "converged" : "sample cap reached");
+        } else {
+            chk(rt_render_until(ctx, 1, spp, per_launch, (uint64_t)seed, noise_target, &frames, &st), "rt_render_until");
+            std::printf("Noise target: %d frames, noise %.6g (%s)\n", frames, st.noise,
+                        st.converged ? "converged" : "sample cap reached");
+        }
         spp = frames;
     }
     for (int f0 = seen[O_NOISE] ? spp : 0; f0 < spp;) {

@@ -91,6 +91,14 @@ def _amd_protos(L, old_rev=False):
         _proto(L, "rt_noise", i, vp, ns_p)
         _proto(L, "rt_render_until", i, vp, i, i, i, u64, f, c_int_p, ns_p)
         _proto(L, "rt_debug_read_samples", i, vp, c_float_p, sz, c_int_p)
+    if not old_rev or hasattr(L, "rt_set_active_tiles"):   # ... or from before the tile masks
+        u8_p, i32_p = ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_int32)
+        _proto(L, "rt_set_active_tiles", i, vp, u8_p, i)
+        _proto(L, "rt_read_tile_frames", i, vp, i32_p, i, c_int_p)
+        _proto(L, "rt_write_tile_frames", i, vp, i32_p, i)
+        _proto(L, "rt_noise_from_tile_sums_frames", i, ts_p, i32_p, i, ns_p)
+        _proto(L, "rt_adaptive_select", i, ts_p, u8_p, i, i, i, f, u8_p, c_int_p)
+        _proto(L, "rt_render_adaptive", i, vp, i, i, i, i, u64, f, c_int_p, ns_p)
     _proto(L, "rt_abi_version", i)
     _proto(L, "rt_create", i, i, c_int_p, ctypes.POINTER(vp))
     _proto(L, "rt_destroy", i, vp)

@@ -104,7 +104,7 @@ OPTIONS = {"box_pretest": 1, "fastdiv": 2, "sph_lds": 3, "big_wg": 4, "chunk_tar
 # rt_debug_last_launch fields
 LAUNCH_FIELDS = ("shape", "block", "fastdiv", "pretest", "lds_bytes", "lds_nodes", "box_records", "staged",
                  "chunks", "spine", "sparse", "sphere_pairs", "leaf_prefetch", "shade_lds", "walk_frac", "bvh_mode",
-                 "box_vnodes", "collapsed", "rebuilt", "box_interior")
+                 "box_vnodes", "collapsed", "rebuilt", "box_interior", "tiles_active")
 BVH_MODES = {"reference": 0, "sah": 1}   # rt.h RT_BVH_*
 TILE_SUM_DTYPE = np.dtype([("m2y", "<f4"), ("y", "<f4"), ("bad", "<u4"), ("pixels", "<u4")])   # rt.h rt_tile_sum
 
@@ -119,6 +119,42 @@ def noise_from_tile_sums(tiles, frames, lib=None):
     if rc != 0:
         raise RTError(rc, "rt_noise_from_tile_sums: frames >= 2 required")
     return s.as_dict()
+
+
+def noise_from_tile_sums_frames(tiles, frames, lib=None):
+    """rt_noise_from_tile_sums_frames (host only): TILE_SUM_DTYPE records, one frame count per tile -> dict."""
+    L = lib or _lib.amd()
+    t = np.ascontiguousarray(tiles, dtype=TILE_SUM_DTYPE)
+    n = np.ascontiguousarray(frames, dtype=np.int32)
+    if n.size != t.size:
+        raise ValueError("one frame count per tile")
+    s = _lib.RtNoiseStats()
+    rc = L.rt_noise_from_tile_sums_frames(t.ctypes.data_as(ctypes.POINTER(_lib.RtTileSum)),
+                                          n.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(t.size), ctypes.byref(s))
+    if rc != 0:
+        raise RTError(rc, "rt_noise_from_tile_sums_frames: every count >= 2 required")
+    return s.as_dict()
+
+
+def adaptive_select(tiles, active, frames, min_frames, target, lib=None):
+    """rt_adaptive_select (host only): which active tiles keep sampling after `frames` frames ->
+    uint8 array, one per tile (active None: all tiles active)."""
+    L = lib or _lib.amd()
+    t = np.ascontiguousarray(tiles, dtype=TILE_SUM_DTYPE)
+    u8_p = ctypes.POINTER(ctypes.c_uint8)
+    a = None if active is None else np.ascontiguousarray(active, dtype=np.uint8)
+    if a is not None and a.size != t.size:
+        raise ValueError("one active byte per tile")
+    out = np.zeros(t.size, np.uint8)
+    n = ctypes.c_int()
+    rc = L.rt_adaptive_select(t.ctypes.data_as(ctypes.POINTER(_lib.RtTileSum)),
+                              None if a is None else a.ctypes.data_as(u8_p), int(t.size), int(frames), int(min_frames),
+                              float(target), out.ctypes.data_as(u8_p), ctypes.byref(n))
+    if rc != 0:
+        raise RTError(rc, "rt_adaptive_select: frames >= 1 and min_frames >= 2 required")
+    return out
+
+
 SHAPES = {0: "fast-lds", 1: "fast-global", 2: "link-lds", 3: "meta-lds", 4: "meta-global", 5: "link-two-level"}
 
 
@@ -191,8 +227,10 @@ class RenderContext:
 
     def last_launch(self):
         """rt_debug_last_launch as a dict (the launch shape the last rt_render took)."""
-        out = (ctypes.c_int * 20)()
-        self._check(self._L.rt_debug_last_launch(self._h, out, 20))
+        out = (ctypes.c_int * len(LAUNCH_FIELDS))()
+        if self._L.rt_debug_last_launch(self._h, out, len(LAUNCH_FIELDS)) != 0:
+            # a library from before tiles_active (tools/lib_ab.py): its 20 fields
+            self._check(self._L.rt_debug_last_launch(self._h, out, 20))
         d = dict(zip(LAUNCH_FIELDS, out[:len(LAUNCH_FIELDS)]))
         d["shape_name"] = SHAPES.get(d["shape"], "?")
         return d
@@ -317,6 +355,39 @@ class RenderContext:
         self._check(self._L.rt_render_until(self._h, int(first_frame), int(max_frames), int(batch_frames),
                                             ctypes.c_uint64(seed), float(target_noise), ctypes.byref(done),
                                             ctypes.byref(s)))
+        return done.value, s.as_dict()
+
+    # -- tile masks, per-tile frame counts and the adaptive loop (rt.h rt_set_active_tiles ...)
+    def set_active_tiles(self, active):
+        """rt_set_active_tiles: one byte per 8x8 tile (row-major); render() then samples only the
+        tiles whose byte is non-zero.  None: every tile again."""
+        if active is None:
+            self._check(self._L.rt_set_active_tiles(self._h, None, 0))
+            return
+        a = np.ascontiguousarray(active, dtype=np.uint8).ravel()
+        self._check(self._L.rt_set_active_tiles(self._h, a.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), int(a.size)))
+
+    def read_tile_frames(self):
+        """rt_read_tile_frames: the frames 1 .. n each tile holds (0 = invalid), int32 per tile."""
+        n = ctypes.c_int()
+        self._check(self._L.rt_read_tile_frames(self._h, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, dtype=np.int32)
+        self._check(self._L.rt_read_tile_frames(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), n.value,
+                                                ctypes.byref(n)))
+        return out
+
+    def write_tile_frames(self, frames):
+        """rt_write_tile_frames: resume a checkpoint's per-tile counts (after write_image / write_moments)."""
+        f = np.ascontiguousarray(frames, dtype=np.int32).ravel()
+        self._check(self._L.rt_write_tile_frames(self._h, f.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(f.size)))
+
+    def render_adaptive(self, target_noise, max_frames, batch_frames, min_frames=16, seed=1, first_frame=1):
+        """rt_render_adaptive -> (frames of the longest-sampled tiles, the final noise dict)."""
+        s = _lib.RtNoiseStats()
+        done = ctypes.c_int()
+        self._check(self._L.rt_render_adaptive(self._h, int(first_frame), int(max_frames), int(batch_frames),
+                                               int(min_frames), ctypes.c_uint64(seed), float(target_noise),
+                                               ctypes.byref(done), ctypes.byref(s)))
         return done.value, s.as_dict()
 
     def read_samples(self):
@@ -447,6 +518,22 @@ class RaytraceExecutor:
         self.numSamples += done
         if stats["converged"]:
             self.samplePerPixel = self.numSamples   # sampleComplete() then runs the listeners
+        return stats
+
+    def raytraceAdaptive(self, noise, batch=16, min_frames=16):
+        """raytraceUntil with the per-tile stopping rule (rt_render_adaptive): a tile stops once it holds
+        at least `min_frames` frames and its own noise estimate is within `noise`; the others go on,
+        up to samplePerPixel frames.  numSamples counts the longest-sampled tiles' frames."""
+        if self.numSamples == 0:
+            self._start = time.time()
+        left = self.samplePerPixel - self.numSamples
+        if left <= 0:
+            raise ValueError("raytraceAdaptive: setSamplePerPixel is the cap and it is reached")
+        done, stats = self.ctx.render_adaptive(noise, left, batch, min_frames=min_frames, seed=self.seed,
+                                               first_frame=self.numSamples + 1)
+        self.numSamples += done
+        if stats["converged"]:
+            self.samplePerPixel = self.numSamples
         return stats
 
     def sampleComplete(self):                    # :144-156
