@@ -278,6 +278,55 @@ int rt_adaptive_select(const rt_tile_sum* tiles, const uint8_t* active_in, int n
 int rt_render_adaptive(rt_ctx* ctx, int first_frame, int max_frames, int batch_frames, int min_frames,
                        uint64_t seed, float target_noise, int* frames_done, rt_noise_stats* last);
 
+/* ---- Variance-guided a-trous preview filter over the sample moments --------------------------
+ * An edge-avoiding wavelet filter whose edge-stopping comes from the measured variance of each
+ * pixel's mean (the moments above), for the first few dozen frames of a render.  It reads the
+ * image, the moments and the per-tile frame counts and writes a buffer of its own: image and
+ * moments keep their bits, and rendering continues as if it had never been called.
+ *
+ * Inputs per pixel: the image's rgb, M2.w, and n = the frame count of the pixel's 8x8 tile (>= 2).
+ * All arithmetic is f32 without contraction, using only + - * / sqrtf fabsf and rt_glsl.h's g_max
+ * (g_max(a, b) = a < b ? b : a), so a float32 restatement matches bit for bit.
+ *   y(C)  = (C.x + C.y) + C.z
+ *   C_0   = rgb,   V_0 = g_max(0, M2.w / ((float)n * (float)(n - 1)))   (variance of the mean of y)
+ * A pixel whose y or M2.w is not finite is bad: it passes through unchanged at every level and is
+ * never used as a tap.  For level i = 0 .. levels-1 with step s = 2^i, at every good pixel p:
+ *   1. Vb(p): over the taps (dy, dx) in {-1,0,1}^2 at spacing 1, row-major (dy outer), that lie in
+ *      the image and are good, with u = k3[dy] * k3[dx], k3 = (1, 2, 1):
+ *        acc = acc + u * V_i(q);  ws = ws + u;   Vb(p) = acc / ws   (acc, ws start at +0).
+ *   2. Taps (dy, dx) in {-2..2}^2, row-major (dy outer), q = p + s * (dx, dy); the centre and taps
+ *      outside the image or bad are skipped.  With h = (1/16, 1/4, 3/8, 1/4, 1/16):
+ *        d  = fabsf(y(p) - y(q)) / (k * sqrtf(Vb(p) + Vb(q)) + 1e-30f)
+ *        w  = (h[dy] * h[dx]) * g_max(0, 1 - d)
+ *        sw = sw + w;   sc = sc + w * (C_i(q).c - C_i(p).c) for c in x, y, z;
+ *        sv = sv + (w * w) * V_i(q)                               (all sums start at +0).
+ *   3. den = h0 + sw with h0 = 9/64;   C_{i+1}(p).c = C_i(p).c + sc / den;
+ *      V_{i+1}(p) = ((h0 * h0) * V_i(p) + sv) / (den * den).
+ * With no neighbour accepted C_{i+1}(p) is C_i(p) exactly; at zero variance the filter is the
+ * identity (unless two pixels' y are equal to the bit).  Output: rgb = C_levels, w = 1.
+ * csrc/rt_denoise_math.h holds these operations once, for the kernels and for rt_denoise_host.
+ *
+ * levels is 1 .. RT_DENOISE_MAX_LEVELS, k > 0 and finite; params NULL = the defaults levels 3,
+ * k 3.  reserved must be 0 (room for guide-buffer terms without another ABI change).
+ * Single-device contexts without rt_set_partition. */
+#define RT_DENOISE_MAX_LEVELS 5
+typedef struct rt_denoise_params { int levels; float k; int reserved[6]; /* must be 0 */ } rt_denoise_params;
+
+/* Queue the filter on the context's stream behind the queued renders.  The result stays in a
+ * buffer of the context until the next rt_denoise, rt_resize, rt_set_moments(ctx, 0) or rt_destroy.
+ * RT_ERR_INVALID_ARG: bad params or non-zero reserved.  RT_ERR_STATE: no image, moments off or
+ * invalid, a tile count < 2, a multi-device context or one under rt_set_partition. */
+int rt_denoise(rt_ctx* ctx, const rt_denoise_params* params);
+
+/* rt_sync, then the filtered image as W*H*4 floats; RT_ERR_STATE with no result held. */
+int rt_read_denoised(rt_ctx* ctx, float* rgba);
+
+/* Host only, no device: the same header's arithmetic over caller arrays.
+ * image / m2: W*H*4 floats.  tile_frames: one count per 8x8 tile, row-major, each >= 2;
+ * n_tiles = ceil(W/8) * ceil(H/8) (RT_ERR_INVALID_ARG otherwise). */
+int rt_denoise_host(const float* image, const float* m2, const int32_t* tile_frames, int n_tiles,
+                    int width, int height, const rt_denoise_params* params, float* rgba_out);
+
 /* Per-frame u_rand_factor for frame index f (0-based) of a seeded render:
  * top 24 bits of splitmix64(seed, f) / 2^24, in [0,1).  Stands in for the
  * reference's (float)Math.random() per frame (RaytraceExecutor.java:124). */

@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "rt_ctx.h"
+#include "rt_denoise.h"
 #include "rt_plan.h"
 #include "bvh_sah.h"
 
@@ -318,6 +319,7 @@ int rt_destroy(rt_ctx* c) {
         dev_free(d.finfo); dev_free(d.f2inner); dev_free(d.f2leaves); dev_free(d.links); dev_free(d.dboxc);
         dev_free(d.gather); dev_free(d.full); dev_free(d.perlin_pk); dev_free(d.sflags);
         dev_free(d.m2); dev_free(d.tile_sums); dev_free(d.node_hits); dev_free(d.tile_list);
+        dev_free(d.dn_px[0]); dev_free(d.dn_px[1]); dev_free(d.dn_vb); dev_free(d.dn_counts);
         comm_destroy(d);
         if (d.ring) (void)hipHostFree(d.ring);
         for (auto& e : d.ring_ev)
@@ -502,6 +504,7 @@ int rt_resize(rt_ctx* c, int w, int h) {
         if (r) return r;
     }
     c->staged_frames = 0;
+    denoise_free(c);        // (alloc_image left every stream idle) the filtered image was the old size's
     set_all_frames(c, 0);   // another image: no tile holds a frame, and a tile mask no longer fits it
     c->mask_set = false;
     c->act_list.clear();
@@ -928,6 +931,7 @@ int rt_set_moments(rt_ctx* c, int on) {
         HIPCHK(c, hipStreamSynchronize(d.stream));
         dev_free(d.m2);
         dev_free(d.tile_sums);
+        denoise_free(c);
         c->moments = false;
         set_all_frames(c, 0);
         return RT_OK;

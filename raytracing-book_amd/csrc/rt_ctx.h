@@ -46,6 +46,9 @@ struct Device {
     DevBuf m2;               // rt_set_moments: per-pixel float4 second moments [local_rows][W] (rt_moments.hip)
     DevBuf tile_sums;        // ... and their per-tile sums (rt_read_tile_sums)
     DevBuf tile_list;        // rt_set_active_tiles: the active tiles' indices, ascending (int32)
+    DevBuf dn_px[2];         // rt_denoise: the levels' ping-pong {r, g, b, V} float4 per pixel (rt_denoise.hip) ...
+    DevBuf dn_vb;            // ... the level's 3x3-averaged variance, one float per pixel ...
+    DevBuf dn_counts;        // ... and the per-tile frame counts (int32, rt_ctx::dn_counts holds the same)
     DevBuf wbuf;             // pooled units (ordered / one chunk): per resident wave 64 x chunk_frames colours
     DevBuf finfo;            // exact near-first walk tables (variant 61)
     DevBuf f2inner, f2leaves;
@@ -192,6 +195,10 @@ struct rt_ctx {
     // (Device::tile_list holds the same on the device)
     bool mask_set = false;
     std::vector<int32_t> act_list;
+    // rt_denoise: which of Device::dn_px holds the filtered image (-1: none held), and the per-tile
+    // counts last copied to Device::dn_counts (copied again only when they change)
+    int dn_result = -1;
+    std::vector<int32_t> dn_counts;
     // the first device's staged colours of the last launch (rt_debug_read_samples): frames, sparse flags
     int staged_frames = 0;
     bool staged_sparse = false;

@@ -1,0 +1,72 @@
+// rt_denoise_host.cpp — the host reference of the preview filter (rt.h rt_denoise_host) and the
+// parameter checks it shares with rt_denoise.  Plain C++, no device: rt_denoise_math.h's functions
+// over caller arrays, level by level, the way rt_denoise.hip's kernels run them.
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "rt/rt.h"
+#include "rt_denoise.h"
+#include "rt_denoise_math.h"
+
+namespace rt_impl {
+
+int denoise_resolve(const rt_denoise_params* p, rt_dn_resolved* out) {
+    out->levels = 3;
+    out->k = 3.0f;
+    if (!p) return RT_OK;
+    for (int r : p->reserved)
+        if (r != 0) return RT_ERR_INVALID_ARG;
+    if (p->levels < 1 || p->levels > RT_DENOISE_MAX_LEVELS) return RT_ERR_INVALID_ARG;
+    if (!(p->k > 0.0f) || !dn_finite(p->k)) return RT_ERR_INVALID_ARG;
+    out->levels = p->levels;
+    out->k = p->k;
+    return RT_OK;
+}
+
+}  // namespace rt_impl
+
+extern "C" int rt_denoise_host(const float* image, const float* m2, const int32_t* tile_frames, int n_tiles, int width,
+                               int height, const rt_denoise_params* params, float* rgba_out) {
+    if (!image || !m2 || !tile_frames || !rgba_out) return RT_ERR_INVALID_ARG;
+    if (width < 1 || height < 1 || width > RT_MAX_IMAGE_DIM || height > RT_MAX_IMAGE_DIM ||
+        (size_t)width * height > ((size_t)1 << 30))
+        return RT_ERR_INVALID_ARG;
+    const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
+    if (n_tiles != tiles_x * tiles_y) return RT_ERR_INVALID_ARG;
+    for (int t = 0; t < n_tiles; t++)
+        if (tile_frames[t] < 2) return RT_ERR_INVALID_ARG;
+    rt_dn_resolved prm;
+    if (rt_impl::denoise_resolve(params, &prm)) return RT_ERR_INVALID_ARG;
+    const size_t n = (size_t)width * height;
+    try {
+        std::vector<rt_dn4> a(n), b(n);
+        std::vector<float> vb(n);
+        for (int y = 0; y < height; y++)
+            for (int x = 0; x < width; x++) {
+                const size_t p = (size_t)y * width + x;
+                rt_dn4 img;
+                std::memcpy(&img, image + p * 4, sizeof(img));
+                a[p] = dn_level0(img, m2[p * 4 + 3], tile_frames[(size_t)(y >> 3) * tiles_x + (x >> 3)]);
+            }
+        rt_dn4 *src = a.data(), *dst = b.data();
+        for (int lv = 0; lv < prm.levels; lv++) {
+            for (int y = 0; y < height; y++)
+                for (int x = 0; x < width; x++) vb[(size_t)y * width + x] = dn_vb(src, width, height, x, y);
+            for (int y = 0; y < height; y++)
+                for (int x = 0; x < width; x++)
+                    dst[(size_t)y * width + x] = dn_filter(src, vb.data(), width, height, x, y, 1 << lv, prm.k);
+            rt_dn4* t = src;
+            src = dst;
+            dst = t;
+        }
+        for (size_t p = 0; p < n; p++) {
+            const rt_dn4 o = src[p];
+            const float px[4] = {o.x, o.y, o.z, 1.0f};
+            std::memcpy(rgba_out + p * 4, px, sizeof(px));
+        }
+    } catch (const std::bad_alloc&) {
+        return RT_ERR_NOMEM;
+    }
+    return RT_OK;
+}

@@ -33,6 +33,12 @@
 // With --adaptive the target holds per 8x8 tile (rt_render_adaptive): a tile stops once it has
 // --min-frames frames (default 16) and its own estimate is within the target, the others go on; it
 // prints "Adaptive: <max frames> frames, <samples> of <W*H*max frames> samples, noise <value> (...)".
+//
+// Preview filter: --denoise turns the sample moments on (the image's bits do not change) and passes the
+// image through rt_denoise (the variance-guided a-trous filter of rt.h; --denoise-levels, --denoise-k)
+// before it is saved: -o receives the filtered image, and so does every --preview update once two
+// frames exist; --raw-output <png> also saves the image as rendered.  One device; works with --noise
+// and --adaptive.
 #include "rt/rt.h"
 #include "rt/rt_scene.h"
 
@@ -58,7 +64,7 @@ struct Opt {
 };
 
 // commons-cli Options in Main.getOptions order (Main.java:43-70)
-enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_N };
+enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_DENOISE, O_DENOISE_LEVELS, O_DENOISE_K, O_RAW_OUT, O_N };
 const Opt kOpts[O_N] = {
     {"h", "help", false, "print help message"},
     {"s", "scene", true, "scene ID"},
@@ -75,6 +81,10 @@ const Opt kOpts[O_N] = {
     {nullptr, "noise", true, "stop once the estimated relative noise is at most this (-spp is the cap)"},
     {nullptr, "adaptive", false, "with --noise: stop sampling each 8x8 tile once it meets the target"},
     {nullptr, "min-frames", true, "with --adaptive: frames every tile gets before it may stop (default 16)"},
+    {nullptr, "denoise", false, "save the image through the variance-guided preview filter (needs 2 frames)"},
+    {nullptr, "denoise-levels", true, "with --denoise: filter levels, 1..5 (default 3)"},
+    {nullptr, "denoise-k", true, "with --denoise: edge-stopping width in standard deviations (default 3)"},
+    {nullptr, "raw-output", true, "with --denoise: also save the unfiltered image to this .png file"},
 };
 
 // HelpFormatter.printHelp("OpenGL Ray Tracer", options): options sorted by key.
@@ -240,6 +250,26 @@ int main(int argc, char** argv) {
     if (seen[O_MIN_FRAMES] && !seen[O_ADAPTIVE]) die("rtrender", "--min-frames goes with --adaptive");
     const int min_frames = seen[O_MIN_FRAMES] ? parse_int(val[O_MIN_FRAMES]) : 16;
     if (min_frames < 2) die("rtrender", "--min-frames must be at least 2");
+    const bool denoise = seen[O_DENOISE];
+    rt_denoise_params dn_params;
+    std::memset(&dn_params, 0, sizeof(dn_params));
+    dn_params.levels = 3;
+    dn_params.k = 3.0f;
+    const std::string raw_output = get(O_RAW_OUT, nullptr);
+    if (!denoise && (seen[O_DENOISE_LEVELS] || seen[O_DENOISE_K] || seen[O_RAW_OUT]))
+        die("rtrender", "--denoise-levels, --denoise-k and --raw-output go with --denoise");
+    if (denoise) {
+        if (seen[O_DENOISE_LEVELS]) dn_params.levels = parse_int(val[O_DENOISE_LEVELS]);
+        if (dn_params.levels < 1 || dn_params.levels > RT_DENOISE_MAX_LEVELS) die("rtrender", "--denoise-levels must be 1..5");
+        if (seen[O_DENOISE_K]) {
+            char* end = nullptr;
+            dn_params.k = std::strtof(val[O_DENOISE_K].c_str(), &end);
+            if (val[O_DENOISE_K].empty() || *end != '\0' || !(dn_params.k > 0.0f) || !(dn_params.k <= 3.0e38f))
+                die("rtrender", "--denoise-k must be a finite number > 0");
+        }
+        if (devices.size() > 1) die("rtrender", "--denoise renders on one device (--devices names more)");
+        if (spp < 2) die("rtrender", "--denoise needs -spp >= 2 (a variance takes two frames)");
+    }
 
     rts_scene* scene = nullptr;
     if (rts_build(scene_id, width, height, (uint64_t)seed, nullptr, &scene) != 0) die("rts_build", rts_last_error());
@@ -272,6 +302,16 @@ int main(int argc, char** argv) {
     rts_spp_uniforms(spp, &sqrt_spp, &recip);   // RaytraceExecutor.setSamplePerPixel
     chk(rt_set_params(ctx, max_depth, info.background, sqrt_spp, recip), "rt_set_params");
     chk(rt_resize(ctx, width, height), "rt_resize");
+    if (denoise) chk(rt_set_moments(ctx, 1), "rt_set_moments");
+    // the image to save: through the filter with --denoise (once every tile holds two frames), else as rendered
+    auto read_shown = [&](float* px, bool filtered) {
+        if (filtered) {
+            chk(rt_denoise(ctx, &dn_params), "rt_denoise");
+            chk(rt_read_denoised(ctx, px), "rt_read_denoised");
+        } else {
+            chk(rt_read_image(ctx, px), "rt_read_image");
+        }
+    };
 
     // RaytraceExecutor.raytrace x samplePerPixel, batched per launch
     auto t0 = std::chrono::steady_clock::now();
@@ -317,7 +357,7 @@ int main(int argc, char** argv) {
         if (!preview.empty() && (f0 % preview_every == 0 || f0 == spp)) {
             // one pass of the window loop: drawResult + GuiRenderer.draw
             rgba.resize((size_t)width * height * 4);
-            chk(rt_read_image(ctx, rgba.data()), "rt_read_image");
+            read_shown(rgba.data(), denoise && f0 >= 2);
             if (rts_save_png(rgba.data(), width, height, preview.c_str()) != 0)
                 uncaught("java.lang.RuntimeException", "Failed to save texture as PNG");
             std::printf("Last raytrace took: %d ms.\n", (int)(ns / 1000000));
@@ -342,12 +382,22 @@ int main(int argc, char** argv) {
     if (!output.empty()) {   // Window.saveImage (Window.java:227-233)
         std::printf("Saving the result to %s...\n", output.c_str());
         std::vector<float> rgba((size_t)width * height * 4);
-        chk(rt_read_image(ctx, rgba.data()), "rt_read_image");
+        read_shown(rgba.data(), denoise);
+        if (denoise) std::printf("Denoise: levels %d, k %g\n", dn_params.levels, (double)dn_params.k);
         if (rts_save_png(rgba.data(), width, height, output.c_str()) != 0)
             uncaught("java.lang.RuntimeException", "Failed to save texture as PNG");
         char abs_path[PATH_MAX];
         const char* shown = realpath(output.c_str(), abs_path) ? abs_path : output.c_str();
         std::printf("A PNG file has been saved to: %s\n", shown);
+    }
+    if (!raw_output.empty()) {
+        std::vector<float> rgba((size_t)width * height * 4);
+        chk(rt_read_image(ctx, rgba.data()), "rt_read_image");
+        if (rts_save_png(rgba.data(), width, height, raw_output.c_str()) != 0)
+            uncaught("java.lang.RuntimeException", "Failed to save texture as PNG");
+        char abs_path[PATH_MAX];
+        const char* shown = realpath(raw_output.c_str(), abs_path) ? abs_path : raw_output.c_str();
+        std::printf("The unfiltered image has been saved to: %s\n", shown);
     }
     rt_destroy(ctx);
     rts_free(scene);

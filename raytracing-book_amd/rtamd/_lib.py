@@ -79,6 +79,11 @@ class RtNoiseStats(ctypes.Structure):
         return {n: getattr(self, n) for n, _ in self._fields_}
 
 
+class RtDenoiseParams(ctypes.Structure):
+    """rt.h rt_denoise_params."""
+    _fields_ = [("levels", ctypes.c_int), ("k", ctypes.c_float), ("reserved", ctypes.c_int * 6)]
+
+
 def _amd_protos(L, old_rev=False):
     vp, sz, i, f, u64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_float, ctypes.c_uint64
     ts_p, ns_p = ctypes.POINTER(RtTileSum), ctypes.POINTER(RtNoiseStats)
@@ -99,6 +104,11 @@ def _amd_protos(L, old_rev=False):
         _proto(L, "rt_noise_from_tile_sums_frames", i, ts_p, i32_p, i, ns_p)
         _proto(L, "rt_adaptive_select", i, ts_p, u8_p, i, i, i, f, u8_p, c_int_p)
         _proto(L, "rt_render_adaptive", i, vp, i, i, i, i, u64, f, c_int_p, ns_p)
+    if not old_rev or hasattr(L, "rt_denoise"):   # ... or from before the preview filter
+        dp_p, i32_p = ctypes.POINTER(RtDenoiseParams), ctypes.POINTER(ctypes.c_int32)
+        _proto(L, "rt_denoise", i, vp, dp_p)
+        _proto(L, "rt_read_denoised", i, vp, c_float_p)
+        _proto(L, "rt_denoise_host", i, c_float_p, c_float_p, i32_p, i, i, i, dp_p, c_float_p)
     _proto(L, "rt_abi_version", i)
     _proto(L, "rt_create", i, i, c_int_p, ctypes.POINTER(vp))
     _proto(L, "rt_destroy", i, vp)

@@ -155,6 +155,41 @@ def adaptive_select(tiles, active, frames, min_frames, target, lib=None):
     return out
 
 
+DENOISE_DEFAULTS = (3, 3.0)   # rt.h rt_denoise: levels, k
+
+
+def _denoise_params(levels, k):
+    """rt_denoise_params for (levels, k); None for both = NULL (the library's defaults)."""
+    if levels is None and k is None:
+        return None
+    p = _lib.RtDenoiseParams()
+    p.levels = DENOISE_DEFAULTS[0] if levels is None else int(levels)
+    p.k = DENOISE_DEFAULTS[1] if k is None else float(k)
+    return ctypes.byref(p)
+
+
+def denoise_host(image, m2, tile_frames, levels=None, k=None, lib=None):
+    """rt_denoise_host (host only, no device): the preview filter over an [H, W, 4] image, its M2 and one
+    frame count per 8x8 tile (row-major; a scalar stands for every tile) -> [H, W, 4] float32."""
+    L = lib or _lib.amd()
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    mom = np.ascontiguousarray(m2, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 4 or mom.shape != img.shape:
+        raise ValueError("image and m2 are [H, W, 4]")
+    H, W = img.shape[:2]
+    nt = ((W + 7) // 8) * ((H + 7) // 8)
+    tf = np.ascontiguousarray(tile_frames, dtype=np.int32).ravel()
+    if tf.size == 1:
+        tf = np.full(nt, tf[0], np.int32)
+    out = np.empty_like(img)
+    rc = L.rt_denoise_host(img.ctypes.data_as(c_float_p), mom.ctypes.data_as(c_float_p),
+                           tf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(tf.size), W, H,
+                           _denoise_params(levels, k), out.ctypes.data_as(c_float_p))
+    if rc != 0:
+        raise RTError(rc, "rt_denoise_host: levels 1..5, k > 0, one count >= 2 per 8x8 tile required")
+    return out
+
+
 SHAPES = {0: "fast-lds", 1: "fast-global", 2: "link-lds", 3: "meta-lds", 4: "meta-global", 5: "link-two-level"}
 
 
@@ -389,6 +424,15 @@ class RenderContext:
                                                int(min_frames), ctypes.c_uint64(seed), float(target_noise),
                                                ctypes.byref(done), ctypes.byref(s)))
         return done.value, s.as_dict()
+
+    # -- the variance-guided preview filter (rt.h rt_denoise)
+    def denoise(self, levels=None, k=None):
+        """rt_denoise + rt_read_denoised: the filtered image as [H, W, 4] float32 (w = 1).  Image and
+        moments are left as they are.  Needs set_moments() and at least two frames in every tile."""
+        self._check(self._L.rt_denoise(self._h, _denoise_params(levels, k)))
+        out = np.empty((self.local_rows, self.width, 4), dtype=np.float32)
+        self._check(self._L.rt_read_denoised(self._h, out.ctypes.data_as(c_float_p)))
+        return out
 
     def read_samples(self):
         """rt_debug_read_samples: the last launch's staged colours, [n_frames, local_rows, W, 4]."""
