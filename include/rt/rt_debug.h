@@ -197,8 +197,48 @@ int rt_debug_get_option(struct rt_ctx* ctx, int option, int* value);
  *   out[17] inner nodes the walk leaves out (option collapse; 0 = none)
  *   out[18] the walk's inner nodes rebuilt over the leaf sequence (option rebuild; 1/0)
  *   out[19] division-free compact box test compiled into the kernel (option box_interior; 1/0)
- * n <= 20 ints are written; returns RT_ERR_STATE before the first render. */
+ *   out[20] tiles the launch sampled: the active tiles of the mask (rt_set_active_tiles), every
+ *           tile without one; 0 when the render launched nothing because no tile was active
+ * n <= 21 ints are written; returns RT_ERR_STATE before the first render. */
 int rt_debug_last_launch(struct rt_ctx* ctx, int* out, int n);
+
+/* Host-only: the launch decision of a render (which kernel instantiation, with how much LDS, and
+ * the rt_debug_last_launch fields it reports) for the deciding inputs in[RT_PK_*] -- the launch's
+ * scalar arguments, and 1/0 for each buffer it has -- as the release library decides it (ab = 0) or
+ * the A/B library (ab = 1: the kernel variants of RT_PK_VARIANT), whichever library is asked.
+ * out[RT_PKO_*] gets the plan and the arguments it edits, info[21] the fields of
+ * rt_debug_last_launch it sets (15..18 stay 0); of a refused launch (out[RT_PKO_OK] 0) only the
+ * edited arguments are given (from RT_PKO_ACC_LDS on), the rest is 0.  table (may be NULL) gets the release library's render kernel
+ * instantiations as (workgroup size, OPT) pairs, *n_table (may be NULL) their count;
+ * RT_ERR_LIMIT if table_cap (pairs) is short. */
+enum {
+    RT_PK_VARIANT = 0,   /* RT_OPTION_KERNEL_VARIANT                                              */
+    RT_PK_BLOCK,         /* workgroup size of the LDS plan: 512 or 1024                           */
+    RT_PK_N_ACTIVE,      /* tiles the launch samples                                              */
+    RT_PK_SAMPLES, RT_PK_SFLAGS, RT_PK_WBUF, RT_PK_TILE_LIST,   /* 1/0: staged colours, sparse flags,
+                            the per-wave slots of ordered launches, a tile mask                   */
+    RT_PK_N_NODES, RT_PK_N_LNODE_F4, RT_PK_LDS_NODE_F4, RT_PK_LDS_END_F4,   /* link nodes, float4 of
+                            their array, float4 of nodes in LDS, float4 end of everything staged  */
+    RT_PK_N_F2INNER, RT_PK_N_F2LEAVES,   /* the near-first walk's tree (A/B)                      */
+    RT_PK_FASTDIV, RT_PK_BOX_ALL_CMP, RT_PK_BOX_INTERIOR, RT_PK_SPH_PAIRS, RT_PK_LEAF_PF,
+    RT_PK_MEDIA_SPH, RT_PK_N_MEDIA, RT_PK_N_SPH_LDS, RT_PK_N_BOX_LDS,
+    /* float4 offsets of the tables in LDS, -1 = not staged */
+    RT_PK_PERLIN_LDS, RT_PK_MEDIA_LDS, RT_PK_SPH_LDS, RT_PK_BOX_CMP_LDS, RT_PK_SPH_MAT_LDS, RT_PK_BOX_MAT_LDS,
+    RT_PK_TEX_LDS,
+    RT_PK_PRETEST,       /* 1/0: the box bounds pre-test is on                                    */
+    RT_PK_N_CHUNKS, RT_PK_SPINE_LEN, RT_PK_WALK_FRAC,   /* reported only                          */
+    RT_PK_N
+};
+enum {
+    RT_PKO_OK = 0,       /* 0: the launch is refused                                              */
+    RT_PKO_SHAPE, RT_PKO_STATS, RT_PKO_POOL, RT_PKO_BLOCK, RT_PKO_OPT, RT_PKO_LDS_BYTES,
+    RT_PKO_ACC_LDS, RT_PKO_LEAF_PF,   /* the arguments as the plan leaves them, and the offsets:  */
+    RT_PKO_PERLIN_LDS, RT_PKO_MEDIA_LDS, RT_PKO_SPH_LDS, RT_PKO_BOX_CMP_LDS, RT_PKO_SPH_MAT_LDS,
+    RT_PKO_BOX_MAT_LDS, RT_PKO_TEX_LDS,
+    RT_PKO_N
+};
+int rt_debug_plan_kernel(const int* in, int n_in, int ab, int* out, int n_out, int* info, int* table, int table_cap,
+                         int* n_table);
 
 /* The BVH the link walk of ctx uses, in the reference's node format (rt_bvh_node): the
  * uploaded one, or in RT_BVH_SAH mode the tree rt_set_bvh_mode builds (validated as by

@@ -141,7 +141,7 @@ struct rt_ctx {
     // per resident wave (env RT_STAGE_TILES) the chunks are ordered (the running
     // mean is handed from wave to wave, rt_kernel.hip wait_chunk); with fewer, a
     // tile's frames would be one long serial chain, so the chunks run in parallel,
-    // stage their per-frame colours (at most sample_budget bytes) and fold_kernel
+    // stage their per-frame colours (at most sample_budget bytes) and the fold (rt_moments.hip)
     // applies the running mean in frame order.  The default stage_tiles stages
     // every chunked launch: with render_stream that measured fastest at N = 1 too
     // (scene 8 -5% against ordered chunks).
@@ -181,7 +181,7 @@ struct rt_ctx {
     int last_launch[RT_LI_N] = {0};
     bool launched = false;
     // Sample moments (rt_set_moments; single-device contexts): every launch is staged and folded by
-    // fold_moments_kernel.  moments_frames = the frames 1 .. n whose moments Device::m2 holds, 0 =
+    // the fold with the moments.  moments_frames = the frames 1 .. n whose moments Device::m2 holds, 0 =
     // invalid (nothing rendered yet, a first_frame gap, the image overwritten or resized).
     bool moments = false;
     int moments_frames = 0;

@@ -10,6 +10,7 @@
 #include "rt/rt.h"
 #include "rt/rt_debug.h"
 #include "rt/rt_types.h"
+#include "rt_plan.h"
 #include "rt_prep.h"
 #include "bvh_sah.h"
 
@@ -213,6 +214,76 @@ int rt_debug_link_nodes(const void* bvh, size_t nbytes, void* out, size_t out_ca
         if (out_cap < L.size() * sizeof(float4)) return RT_ERR_INVALID_ARG;
         if (!L.empty()) std::memcpy(out, L.data(), L.size() * sizeof(float4));
     }
+    return RT_OK;
+}
+
+int rt_debug_plan_kernel(const int* in, int n_in, int ab, int* out, int n_out, int* info, int* table, int table_cap,
+                         int* n_table) {
+    if (!in || !out || !info || n_in != RT_PK_N || n_out != RT_PKO_N || table_cap < 0) return RT_ERR_INVALID_ARG;
+    if (n_table) *n_table = N_RENDER_KERNELS;
+    if (table) {
+        if (table_cap < N_RENDER_KERNELS) return RT_ERR_LIMIT;
+        for (int i = 0; i < N_RENDER_KERNELS; i++) {
+            table[2 * i] = RENDER_KERNELS[i].block;
+            table[2 * i + 1] = RENDER_KERNELS[i].opt;
+        }
+    }
+    static float4 there[1];   // plan_kernel asks only whether a buffer is there
+    rt_kernel_args a = {};
+    a.variant = in[RT_PK_VARIANT];
+    a.block = in[RT_PK_BLOCK];
+    a.n_active = in[RT_PK_N_ACTIVE];
+    a.samples = in[RT_PK_SAMPLES] ? there : nullptr;
+    a.sflags = in[RT_PK_SFLAGS] ? (uint8_t*)there : nullptr;
+    a.wbuf = in[RT_PK_WBUF] ? there : nullptr;
+    a.tile_list = in[RT_PK_TILE_LIST] ? (const int*)there : nullptr;
+    a.n_nodes = in[RT_PK_N_NODES];
+    a.n_lnode_f4 = in[RT_PK_N_LNODE_F4];
+    a.lds_node_f4 = in[RT_PK_LDS_NODE_F4];
+    a.lds_end_f4 = in[RT_PK_LDS_END_F4];
+    a.n_f2inner = in[RT_PK_N_F2INNER];
+    a.n_f2leaves = in[RT_PK_N_F2LEAVES];
+    a.fastdiv = in[RT_PK_FASTDIV];
+    a.box_all_cmp = in[RT_PK_BOX_ALL_CMP];
+    a.box_interior = in[RT_PK_BOX_INTERIOR];
+    a.sph_pairs = in[RT_PK_SPH_PAIRS];
+    a.leaf_pf = in[RT_PK_LEAF_PF];
+    a.media_sph = in[RT_PK_MEDIA_SPH];
+    a.n_media = in[RT_PK_N_MEDIA];
+    a.n_sph_lds = in[RT_PK_N_SPH_LDS];
+    a.n_box_lds = in[RT_PK_N_BOX_LDS];
+    a.perlin_lds = in[RT_PK_PERLIN_LDS];
+    a.media_lds = in[RT_PK_MEDIA_LDS];
+    a.sph_lds = in[RT_PK_SPH_LDS];
+    a.box_cmp_lds = in[RT_PK_BOX_CMP_LDS];
+    a.sph_mat_lds = in[RT_PK_SPH_MAT_LDS];
+    a.box_mat_lds = in[RT_PK_BOX_MAT_LDS];
+    a.tex_lds = in[RT_PK_TEX_LDS];
+    a.box_margin = in[RT_PK_PRETEST] ? 1.0f : 0.0f;
+    a.n_chunks = in[RT_PK_N_CHUNKS];
+    a.spine_len = in[RT_PK_SPINE_LEN];
+    a.walk_frac = in[RT_PK_WALK_FRAC];
+    const KernelPlan k = plan_kernel(a, ab != 0);
+    std::memset(out, 0, sizeof(int) * RT_PKO_N);
+    std::memset(info, 0, sizeof(int) * RT_LI_N);
+    out[RT_PKO_OK] = k.ok;
+    out[RT_PKO_PERLIN_LDS] = a.perlin_lds;
+    out[RT_PKO_MEDIA_LDS] = a.media_lds;
+    out[RT_PKO_SPH_LDS] = a.sph_lds;
+    out[RT_PKO_BOX_CMP_LDS] = a.box_cmp_lds;
+    out[RT_PKO_SPH_MAT_LDS] = a.sph_mat_lds;
+    out[RT_PKO_BOX_MAT_LDS] = a.box_mat_lds;
+    out[RT_PKO_TEX_LDS] = a.tex_lds;
+    out[RT_PKO_ACC_LDS] = a.acc_lds;
+    out[RT_PKO_LEAF_PF] = a.leaf_pf;
+    if (!k.ok) return RT_OK;
+    out[RT_PKO_SHAPE] = k.shape;
+    out[RT_PKO_STATS] = k.stats;
+    out[RT_PKO_POOL] = k.pool;
+    out[RT_PKO_BLOCK] = k.block;
+    out[RT_PKO_OPT] = k.opt;
+    out[RT_PKO_LDS_BYTES] = (int)k.lds;
+    std::memcpy(info, k.info, sizeof(int) * RT_LI_N);
     return RT_OK;
 }
 

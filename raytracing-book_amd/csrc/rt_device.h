@@ -219,23 +219,27 @@ struct rt_kernel_args {
 enum { RT_LI_SHAPE = 0, RT_LI_BLOCK, RT_LI_FASTDIV, RT_LI_PRETEST, RT_LI_LDS, RT_LI_LDS_NODES, RT_LI_COMPACT,
        RT_LI_STAGED, RT_LI_CHUNKS, RT_LI_SPINE, RT_LI_SPARSE, RT_LI_SPAIR, RT_LI_LEAF_PF, RT_LI_SHADE_LDS, RT_LI_WALK_FRAC, RT_LI_BVH_MODE, RT_LI_VNODES, RT_LI_COLLAPSED, RT_LI_REBUILT, RT_LI_BOXQ, RT_LI_TILES_ACTIVE, RT_LI_N = 21 };
 
+// The launch shapes (info[RT_LI_SHAPE]; rt_plan.h plan_kernel chooses one).  The release library
+// launches the two link shapes with pooled samples; the A/B library (rt_kernel_variants.hip) also
+// the others, and RT_SHAPE_LINK_LDS with one pixel per lane.
+enum { RT_SHAPE_FAST_LDS = 0, RT_SHAPE_FAST_GLOBAL, RT_SHAPE_LINK_LDS, RT_SHAPE_META_LDS, RT_SHAPE_META_GLOBAL,
+       RT_SHAPE_LINK_TL };
+#define RT_FAST_STACK 16   // the near-first walk's per-lane stack (shorts in LDS; A/B library)
 #ifdef RT_AB_KNOBS
 // A/B library only (rt_kernel_variants.hip): the structures the release library does not ship
-#define RT_FAST_STACK 16   // the near-first walk's per-lane stack (shorts in LDS)
-enum { RT_AB_SHAPE_FAST_LDS = 0, RT_AB_SHAPE_FAST_GLOBAL, RT_AB_SHAPE_LINK_PIXEL, RT_AB_SHAPE_META_LDS,
-       RT_AB_SHAPE_META_GLOBAL };
 int rt_launch_render_ab(int shape, rt_kernel_args& a, const rt_kernel_args* d, size_t lds, bool stats, void* stream);
 #endif
 // launcher implemented in rt_kernel.hip
 int rt_resident_waves(void);   // waves a render launch keeps resident on the current device (its grid, at most)
-// sets a.acc_lds; info (may be NULL): RT_LI_* of the launch; moments (may be NULL): the per-pixel
-// float4 second moments a staged launch's fold also updates (fold_moments_kernel for fold_kernel)
+// plans the launch (rt_plan.h plan_kernel, which edits a); info (may be NULL): RT_LI_* of the launch;
+// moments (may be NULL): the per-pixel float4 second moments a staged launch's fold also updates
 int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int* info, void* moments = nullptr);
 // launchers implemented in rt_moments.hip
-// a staged launch's colours (a.samples, a.sflags) folded into a.image and moments [n_pixels] float4
+// a staged launch's colours (a.samples, a.sflags) folded into a.image and, unless NULL (the mean
+// alone), moments [n_pixels] float4
 int rt_launch_fold_moments(const rt_kernel_args& a, void* moments, void* stream);
 // the same under a tile mask (a.tile_list, a.n_active): one wave per active tile, only its pixels' words
-// are read or written; moments may be NULL (the mean alone, fold_kernel's operations)
+// are read or written; moments may be NULL
 int rt_launch_fold_tiles(const rt_kernel_args& a, void* moments, void* stream);
 // image, moments [local_rows][width] float4 -> out: one rt_tile_sum per 8x8 tile, row-major
 int rt_launch_tile_sums(const void* image, const void* moments, int width, int local_rows, void* out, void* stream);

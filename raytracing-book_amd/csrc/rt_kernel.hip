@@ -203,6 +203,9 @@ __device__ __forceinline__ void render_stream(const KP& P, const float4* __restr
                     float4* px = reinterpret_cast<float4*>(P.image) + (size_t)(g.ly0 + (lane >> 3)) * P.width +
                                  g.tx0 + (lane & 7);
                     float4 prev = *px;
+                    // mean_step (rt_fold_step.h), written out: calling it here leaves every instance's
+                    // registers as they are but swaps the operands of two of these adds and renames
+                    // registers elsewhere, and the render kernels' instructions are pinned
                     for (int f = g.f0; f < g.f1; f++) {
                         const float4 c4 = ws[(f - g.f0) * 64 + lane];
                         const int fcnt = P.first_frame + f;
@@ -403,7 +406,7 @@ __device__ __forceinline__ void render_stream(const KP& P, const float4* __restr
                 const float4 c4 = make_float4(cur3.x, cur3.y, cur3.z, 0.0f);
                 if (staged) {
                     // sparse staging (P.sflags): every sample writes one flag byte, and only a colour
-                    // that is not exactly (+0, +0, +0) is stored; fold_kernel reads a clear flag as
+                    // that is not exactly (+0, +0, +0) is stored; the fold (rt_moments.hip) reads a clear flag as
                     // that zero colour -- the same values, so the same running mean
                     if (sparse) {
                         const bool nz = (__float_as_uint(cur3.x) | __float_as_uint(cur3.y) | __float_as_uint(cur3.z)) != 0u;
@@ -472,62 +475,6 @@ __global__ void __launch_bounds__(BLOCK, MINW) render_persistent(const KP* __res
     }
 }
 
-// Staged-chunk epilogue: the running mean of compute.glsl:355 over the launch's
-// frames, in frame order, per pixel: (prev*(n-1)+cur)/n -- the operations the
-// ordered path applies in LDS, so the same bits.
-__global__ void __launch_bounds__(256) fold_kernel(const KP* __restrict__ Pp) {
-    const KP& P = *Pp;
-    const size_t pix = (size_t)blockIdx.x * 256 + threadIdx.x;
-    if (pix >= P.n_pixels) return;
-    float4* px = reinterpret_cast<float4*>(P.image) + pix;
-    float4 prev = *px;
-    const float4* s = P.samples + pix;
-    if (P.sflags) {   // sparse staging: a clear flag is the colour (+0, +0, +0), never stored
-        // eight frames at a time: their flags, then the set ones' colours, all loads issued
-        // before the eight folds (which stay in frame order)
-        const uint8_t* fl = P.sflags + pix;
-        int f = 0;
-        for (; f + 8 <= P.n_frames; f += 8) {
-            uint32_t fb[8];
-            float4 cur[8];
-#pragma unroll
-            for (int k = 0; k < 8; k++) fb[k] = fl[(size_t)(f + k) * P.n_pixels];
-#pragma unroll
-            for (int k = 0; k < 8; k++)
-                cur[k] = fb[k] ? s[(size_t)(f + k) * P.n_pixels] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-#pragma unroll
-            for (int k = 0; k < 8; k++) {
-                const int fc = P.first_frame + f + k;
-                const float n1 = (float)(fc - 1), n = (float)fc;
-                prev.x = (prev.x * n1 + cur[k].x) / n;
-                prev.y = (prev.y * n1 + cur[k].y) / n;
-                prev.z = (prev.z * n1 + cur[k].z) / n;
-                prev.w = 1.0f;
-            }
-        }
-        for (; f < P.n_frames; f++) {
-            const float4 cur = fl[(size_t)f * P.n_pixels] ? s[(size_t)f * P.n_pixels] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            const int fc = P.first_frame + f;
-            const float n1 = (float)(fc - 1), n = (float)fc;
-            prev.x = (prev.x * n1 + cur.x) / n;
-            prev.y = (prev.y * n1 + cur.y) / n;
-            prev.z = (prev.z * n1 + cur.z) / n;
-            prev.w = 1.0f;
-        }
-    } else {
-        for (int f = 0; f < P.n_frames; f++) {
-            const float4 cur = s[(size_t)f * P.n_pixels];
-            const int fc = P.first_frame + f;
-            const float n1 = (float)(fc - 1), n = (float)fc;
-            prev.x = (prev.x * n1 + cur.x) / n;
-            prev.y = (prev.y * n1 + cur.y) / n;
-            prev.z = (prev.z * n1 + cur.z) / n;
-            prev.w = 1.0f;
-        }
-    }
-    *px = prev;
-}
-
 // Gathered stripe blocks [world][padded_rows][W] float4 -> the image [H][W] (row 0 = top):
 // row y belongs to stripe s = y / stripe_rows, rendered by rank s % world as its local row
 // (s / world) * stripe_rows + y % stripe_rows (rt_set_partition).  One thread per pixel,
@@ -575,159 +522,65 @@ int rt_resident_waves(void) {
     return cus * 2 * (512 / 64);   // every shape: at most 2 workgroups of 512 per CU (launch_persistent)
 }
 
-int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int* info, void* moments) {
-    if (a.local_rows <= 0 || a.width <= 0 || a.n_frames <= 0) return 0;
-    if (a.n_active <= 0) return -1;   // the units divide by it (unit_geo); the caller skips an empty mask
-    hipStream_t st = (hipStream_t)stream;
-    // The release library has one kernel structure (tests/test_gpu_*.py pin it to the oracle):
-    // pooled samples streamed over units with walks and shading in batches (render_stream) over
-    // link-format nodes staged in LDS with the Perlin table, media, sphere and box records the
-    // host placed after them (a.lds_end_f4), 4 waves per SIMD, as 2 x 512 or 1 x 1024 threads
-    // per CU (a.block); when the nodes do not fit (a.lds_node_f4 < 2 n_nodes) the two-level
-    // walk reads the nodes below the staged top levels from global memory (1024 threads).
-    // Each in a shared-reciprocal division form (a.fastdiv) and the plain one.
-    // The A/B build (RT_AB_KNOBS) adds the other structures, all bit-identical
-    // (RT_OPTION_KERNEL_VARIANT): 37 the link walk with one pixel per lane (the round-1
-    // default), 30 threaded meta-word nodes (LDS when they fit, else global), 61 the exact
-    // near-first stack walk, and the region-timer stats twins 39 / 38 / 31 / 69.
-    enum { FAST_LDS, FAST_GLOBAL, LINK_LDS, META_LDS, META_GLOBAL, LINK_TL } shape = LINK_LDS;
-    size_t staged = (size_t)a.lds_end_f4 * 16;
-    bool stats = false, pool = true;
-    const bool tl = a.n_lnode_f4 > 0 && a.lds_node_f4 < 2 * a.n_nodes;
-    if (tl) shape = LINK_TL;
+// Launches the planned kernel: the RENDER_KERNELS entry (rt_plan.h; <MINW, STATS, BLOCK, OPT>, each
+// with its mask twin, and the stats twins in the A/B build only) that matches the plan, or -1.
+static int launch_planned(const rt_impl::KernelPlan& k, rt_kernel_args& a, const rt_kernel_args* d, hipStream_t st) {
+    if (!k.pool || (k.shape != RT_SHAPE_LINK_LDS && k.shape != RT_SHAPE_LINK_TL)) {
 #ifdef RT_AB_KNOBS
-    stats = a.variant == 38 || a.variant == 31 || a.variant == 69 || a.variant == 39;
-    pool = a.variant == 0 || a.variant == 39;
-    if (a.variant == 61 || a.variant == 69) {
-        const size_t stack_b = (size_t)RT_FAST_STACK * 512 * sizeof(short);
-        const size_t tree_b = (size_t)a.n_f2inner * 64 + (size_t)((a.n_f2leaves + 1) / 2) * 16;
-        shape = tree_b + stack_b <= RT_LDS_DYN_BYTES ? FAST_LDS : FAST_GLOBAL;
-        staged = shape == FAST_LDS ? tree_b + stack_b : stack_b;
-    } else if (a.variant == 30 || a.variant == 31 || (!pool && tl)) {
-        // threaded meta-word nodes, then what the host placed after the link-format nodes
-        const size_t lds_t = (size_t)a.n_nodes * sizeof(rt_dnode);
-        staged = std::max(lds_t, staged);
-        shape = (lds_t <= RT_LDS_NODE_BYTES && staged <= RT_LDS_DYN_BYTES) ? META_LDS : META_GLOBAL;
+        return rt_launch_render_ab(k.shape, a, d, k.lds, k.stats, st);
+#else
+        return -1;
+#endif
     }
-    if (shape == FAST_LDS || shape == FAST_GLOBAL || shape == META_GLOBAL) {   // nothing else staged
-        if (shape == META_GLOBAL) staged = 0;
-        a.perlin_lds = a.media_lds = a.sph_lds = a.box_cmp_lds = -1;
-        a.sph_mat_lds = a.box_mat_lds = a.tex_lds = -1;
+#define RT_X1(STATS, BLOCK, OPT)              \
+    if (k.block == BLOCK && k.opt == (OPT))  \
+        return launch_persistent(render_persistent<4, STATS, BLOCK, (OPT)>, BLOCK, k.lds, a, d, st);
+    if (!k.stats) {
+#define RT_X(BLOCK, OPT) RT_X1(false, BLOCK, OPT) RT_X1(false, BLOCK, (OPT) | RT_OPT_MASK)
+        RT_RENDER_KERNELS(RT_X)
+#undef RT_X
+    }
+#ifdef RT_AB_KNOBS
+    else {
+#define RT_X(BLOCK, OPT) \
+    RT_X1(true, BLOCK, (OPT) & ~RT_OPT_BOXQ) RT_X1(true, BLOCK, ((OPT) & ~RT_OPT_BOXQ) | RT_OPT_MASK)
+        RT_RENDER_KERNELS(RT_X)
+#undef RT_X
     }
 #endif
-    if ((shape == LINK_LDS || shape == LINK_TL) && staged > (a.block == 1024 ? RT_LDS_BIG_BYTES : RT_LDS_DYN_BYTES))
-        return -1;
-    if (shape == LINK_TL && (a.block != 1024 || !pool)) return -1;
-    if (pool && !a.samples && !a.wbuf) return -1;   // pooled ordered / one-chunk units need the per-wave slots
-    // the leaf record prefetch reads only tables that are staged (the A/B shapes above may drop them)
-    a.leaf_pf = (a.leaf_pf && a.box_all_cmp && a.sph_lds >= 0 && a.box_cmp_lds > a.sph_lds &&
-                 (a.n_media == 0 || a.media_lds >= 0)) ? 1 : 0;
-    // the one-pixel-per-lane kernels (A/B) keep the lanes' running means in LDS after what is staged
-    a.acc_lds = (int)(staged / 16);
-    const size_t lds = staged + (pool ? 0 : RT_LDS_ACC_BYTES);
-    if (info) {
-        info[RT_LI_SHAPE] = (int)shape;
-        info[RT_LI_BLOCK] = (shape == LINK_LDS || shape == LINK_TL) ? a.block : 512;
-        info[RT_LI_FASTDIV] = a.fastdiv;
-        info[RT_LI_PRETEST] = a.box_margin > 0.0f;
-        info[RT_LI_LDS] = (int)lds;
-        info[RT_LI_LDS_NODES] = (shape == LINK_LDS || shape == LINK_TL) ? a.lds_node_f4 / 2 : 0;
-        info[RT_LI_COMPACT] = a.box_all_cmp + 2 * (a.box_cmp_lds >= 0);
-        info[RT_LI_STAGED] = a.samples != nullptr;
-        info[RT_LI_CHUNKS] = a.n_chunks;
-        info[RT_LI_SPINE] = pool ? a.spine_len : 0;
-        info[RT_LI_SPARSE] = a.samples && a.sflags ? 1 : 0;
-        info[RT_LI_SPAIR] = (pool && shape == LINK_LDS && a.sph_lds >= 0 &&
-                             ((a.sph_pairs && !a.box_all_cmp) || (a.sph_pairs == 2 && a.fastdiv))) ? 1 : 0;
-        info[RT_LI_LEAF_PF] = (pool && (shape == LINK_LDS || shape == LINK_TL)) ? a.leaf_pf : 0;
-        info[RT_LI_WALK_FRAC] = a.walk_frac;
-        info[RT_LI_TILES_ACTIVE] = a.n_active;
-        info[RT_LI_SHADE_LDS] = (a.sph_mat_lds >= 0) + 2 * (a.box_mat_lds >= 0) + 4 * (a.tex_lds >= 0);
-    }
+#undef RT_X1
+    return -1;
+}
+
+int rt_launch_render(rt_kernel_args& a, rt_kernel_args* dargs, void* stream, int* info, void* moments) {
+    if (a.local_rows <= 0 || a.width <= 0 || a.n_frames <= 0) return 0;
+    hipStream_t st = (hipStream_t)stream;
+#ifdef RT_AB_KNOBS
+    const bool ab = true;
+#else
+    const bool ab = false;
+#endif
+    const rt_impl::KernelPlan k = rt_impl::plan_kernel(a, ab);
+    if (!k.ok) return -1;
+    if (info)
+        for (int i = 0; i < RT_LI_N; i++)
+            if (i < RT_LI_BVH_MODE || i > RT_LI_REBUILT) info[i] = k.info[i];   // (those four are rt_render's)
     // Arguments live in device memory: the by-value kernarg struct would be copied
     // to scratch as soon as a non-inlined device function takes its address.
     // `a` is a pinned staging slot; same-stream ordering makes one device slot
     // safe to reuse per launch.
     if (hipMemcpyAsync(dargs, &a, sizeof(a), hipMemcpyHostToDevice, st) != hipSuccess) return -1;
-    const rt_kernel_args* d = (const rt_kernel_args*)dargs;
     // the work-unit counter, then (ordered chunks) the tiles' published chunk counts
     const int n_tiles = ((a.width + 7) / 8) * ((a.local_rows + 7) / 8);
     if (hipMemsetAsync(a.tile_counter, 0, sizeof(int), st) != hipSuccess) return -1;
     if (a.n_chunks > 1 && !a.samples &&
         hipMemsetAsync(a.tile_done, 0, sizeof(unsigned) * (size_t)n_tiles, st) != hipSuccess)
         return -1;
-
-    constexpr int SM = RT_OPT_POOL | RT_OPT_SM | RT_OPT_STREAM;
-    // the instantiations: <MINW, STATS, BLOCK, OPT> (stats twins in the A/B build only)
-#ifdef RT_AB_KNOBS
-#define RT_KERNEL1(BLOCK, OPT)                                                                           \
-    (stats ? launch_persistent(render_persistent<4, true, BLOCK, (OPT) & ~RT_OPT_BOXQ>, BLOCK, lds, a, d, st)  \
-           : launch_persistent(render_persistent<4, false, BLOCK, OPT>, BLOCK, lds, a, d, st))
-#else
-#define RT_KERNEL1(BLOCK, OPT) launch_persistent(render_persistent<4, false, BLOCK, OPT>, BLOCK, lds, a, d, st)
-#endif
-    // ... each with its twin for a launch under a tile mask (RT_OPT_MASK)
-#define RT_KERNEL(BLOCK, OPT) (a.tile_list ? RT_KERNEL1(BLOCK, (OPT) | RT_OPT_MASK) : RT_KERNEL1(BLOCK, OPT))
-    int rc = -1;
-    // the default launch's configuration (RT_OPT_STD) holds: the kernels with it compiled in
-    const bool std_cfg = a.samples && a.sflags && a.media_sph &&
-                         (a.n_sph_lds == 0 || (a.sph_lds >= 0 && a.sph_mat_lds >= 0)) &&
-                         (a.n_media == 0 || a.media_lds >= 0) && (a.n_box_lds == 0 || a.box_cmp_lds >= 0) &&
-                         (!a.box_all_cmp || (a.leaf_pf && a.box_mat_lds >= 0)) && a.tex_lds >= 0;
-    if (info)   // the RT_OPT_BOXQ kernels below
-        info[RT_LI_BOXQ] = (pool && !stats && a.box_interior && a.fastdiv && a.box_all_cmp && std_cfg &&
-                            shape == LINK_LDS && a.sph_pairs != 2) ? 1 : 0;
-    // the link shapes x (shared-reciprocal division | plain) x (compact boxes | full box records)
-#define RT_LINK4(BLOCK, OPT)                                                                                 \
-    (a.fastdiv ? (a.box_all_cmp ? (std_cfg ? (a.box_interior   /* not the two-level kernel: SGPR spills */          \
-                                                  ? RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD | RT_OPT_BOXC | RT_OPT_STD | (((OPT) & RT_OPT_TL) ? 0 : RT_OPT_BOXQ)) \
-                                                  : RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD | RT_OPT_BOXC | RT_OPT_STD))      \
-                                           : RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD | RT_OPT_BOXC))                         \
-                                : (std_cfg ? RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD | RT_OPT_STD)                            \
-                                           : RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD)))                                      \
-               : (a.box_all_cmp ? RT_KERNEL(BLOCK, (OPT) | RT_OPT_BOXC) : RT_KERNEL(BLOCK, (OPT))))
-    // ... and, for a scene whose leaves are mostly sphere pairs (a.sph_pairs), without compact boxes
-#define RT_LINK4S(BLOCK, OPT)                                                                                 \
-    ((a.sph_pairs == 2 && a.box_all_cmp && a.fastdiv) ? RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD | RT_OPT_BOXC | RT_OPT_SPAIR) : \
-    (a.sph_pairs && !a.box_all_cmp)                                                                          \
-         ? (a.fastdiv ? (std_cfg ? RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD | RT_OPT_SPAIR | RT_OPT_STD)                      \
-                                 : RT_KERNEL(BLOCK, (OPT) | RT_OPT_FD | RT_OPT_SPAIR))                                \
-                      : RT_KERNEL(BLOCK, (OPT) | RT_OPT_SPAIR))                                                       \
-         : RT_LINK4(BLOCK, OPT))
-    switch (shape) {
-        case LINK_LDS:
-            if (!pool) {
-#ifdef RT_AB_KNOBS
-                rc = rt_launch_render_ab(RT_AB_SHAPE_LINK_PIXEL, a, d, lds, stats, st);
-#endif
-            } else if (a.block == 1024) {
-                rc = RT_LINK4S(1024, SM);
-            } else {
-                rc = RT_LINK4S(512, SM);
-            }
-            break;
-        case LINK_TL: rc = RT_LINK4(1024, SM | RT_OPT_TL); break;
-#ifdef RT_AB_KNOBS
-        case FAST_LDS: rc = rt_launch_render_ab(RT_AB_SHAPE_FAST_LDS, a, d, lds, stats, st); break;
-        case FAST_GLOBAL: rc = rt_launch_render_ab(RT_AB_SHAPE_FAST_GLOBAL, a, d, lds, stats, st); break;
-        case META_LDS: rc = rt_launch_render_ab(RT_AB_SHAPE_META_LDS, a, d, lds, stats, st); break;
-        case META_GLOBAL: rc = rt_launch_render_ab(RT_AB_SHAPE_META_GLOBAL, a, d, lds, stats, st); break;
-#endif
-        default: break;
-    }
-#undef RT_KERNEL
-#undef RT_KERNEL1
-#undef RT_LINK4
-#undef RT_LINK4S
-    if (rc) return rc;
-    if (a.samples && a.tile_list) {   // under a tile mask: the same folds over the active tiles' pixels alone
-        if (rt_launch_fold_tiles(a, moments, stream)) return -1;
-    } else if (a.samples && moments) {   // ... and the second moments (rt_moments.hip), the same mean
-        if (rt_launch_fold_moments(a, moments, stream)) return -1;
-    } else if (a.samples) {   // staged chunks: the running mean over the launch's frames
-        const unsigned blocks = (unsigned)((a.n_pixels + 255) / 256);
-        hipLaunchKernelGGL(fold_kernel, dim3(blocks), dim3(256), 0, st, d);
-    }
+    if (const int rc = launch_planned(k, a, dargs, st)) return rc;
+    // staged chunks: the running mean (and the second moments) over the launch's frames, under a
+    // tile mask over the active tiles' pixels alone (rt_moments.hip)
+    if (a.samples && (a.tile_list ? rt_launch_fold_tiles(a, moments, stream) : rt_launch_fold_moments(a, moments, stream)))
+        return -1;
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 

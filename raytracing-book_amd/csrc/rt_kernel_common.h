@@ -15,36 +15,20 @@
 
 #include "rt/rt_glsl.h"
 #include "rt_device.h"
+#include "rt_fold_step.h"
+#include "rt_plan.h"
 
 
 namespace {
 
 typedef rt_kernel_args KP;
 
-// OPT bits of the kernel templates
+// (the OPT bits of the kernel templates: rt_plan.h RT_OPT_*, with the table of instantiations)
 // the branchless walk (link_walk_part BL) in the sphere-pair STD kernels too (scene 0: -0.8%,
 // profiles/r06_ae_bl_spair_lib_ab.log); the compact-box STD kernels always
 #ifndef RT_BL_SPAIR
 #define RT_BL_SPAIR 1
 #endif
-#define RT_OPT_POOL 1   // pooled units (render_pool): without it a lane owns a pixel (variant 37)
-#define RT_OPT_SM 2     // with RT_OPT_POOL and the link walk: walks and shading in batches (render_stream)
-#define RT_OPT_FD 4     // with RT_OPT_SM: the scene is in the shared-reciprocal division regime (P.fastdiv)
-#define RT_OPT_STREAM 8 // with RT_OPT_SM: the wave streams over units (render_stream) instead of one at a time
-#define RT_OPT_TL 16    // with RT_OPT_STREAM: two-level walk (top levels in LDS, the rest of the nodes global)
-#define RT_OPT_BOXC 32  // with RT_OPT_STREAM: every box has a compact record (box_test_compact), no full box test
-#define RT_OPT_SPAIR 64 // with RT_OPT_STREAM: leaves of two spheres tested at once (leaf_prims_t; most leaves are)
-#define RT_OPT_BOXQ 256 // with RT_OPT_FD, RT_OPT_BOXC and RT_OPT_STD: the compact box test with one reciprocal per
-                        // axis and no division per face (box_test_compact_q; option box_interior)
-#define RT_OPT_MASK 512 // with RT_OPT_STREAM: the units run over the active tiles of a tile mask (P.tile_list, P.n_active;
-                        // rt_kernel.hip unit_geo); without it the code is the unmasked kernel's, unchanged
-#define RT_OPT_STD 128  // the default launch's configuration, compiled in (rt_launch_render std_config takes these
-                        // kernels when it holds): staged chunks with sparse staging (P.samples, P.sflags), every
-                        // medium bounded by a sphere (P.media_sph; no out-of-line boundary call), the leaf and
-                        // shading tables in LDS (spheres, media, box records, sphere materials, texture
-                        // descriptors) and with RT_OPT_BOXC the compact boxes' materials and the leaf record
-                        // prefetch (P.leaf_pf: the leaf stage holds only the prefetched forms).  Fewer wave-uniform
-                        // flags live through the rounds: the C3 kernel 128 -> 117 VGPRs, SGPR spills 34 -> 0
 
 // The kernels' dynamic LDS (render_persistent stages the BVH there, then the
 // Perlin table and the media records when P.perlin_lds / P.media_lds >= 0).

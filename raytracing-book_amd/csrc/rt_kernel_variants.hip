@@ -427,16 +427,11 @@ __device__ __forceinline__ void render_pixel(const KP& P, const float4* __restri
         }
         v3 cur;
         if (bounce<LINK, STATS, FAST, OPT>(P, nodes, fc, S, fx, fy, cur, st)) {
-            if (P.samples) {   // staged chunks: fold_kernel applies the running mean in frame order
+            if (P.samples) {   // staged chunks: the fold (rt_moments.hip) applies the running mean in frame order
                 P.samples[(size_t)f * P.n_pixels + pix] = make_float4(cur.x, cur.y, cur.z, 0.0f);
             } else {
-                int fc = P.first_frame + f;
-                float n1 = (float)(fc - 1), n = (float)fc;
                 float4 prev = *acc;
-                prev.x = (prev.x * n1 + cur.x) / n;
-                prev.y = (prev.y * n1 + cur.y) / n;
-                prev.z = (prev.z * n1 + cur.z) / n;
-                prev.w = 1.0f;
+                mean_step(prev, make_float4(cur.x, cur.y, cur.z, 0.0f), P.first_frame + f);
                 *acc = prev;
             }
             f++;
@@ -594,15 +589,7 @@ __global__ void __launch_bounds__(BLOCK, MINW) render_persistent_ab(const KP* __
             if (valid) {
                 float4* px = reinterpret_cast<float4*>(P.image) + (size_t)lr * P.width + x;
                 float4 prev = *px;
-                for (int f = f0; f < f1; f++) {
-                    const float4 cur = wslot[(f - f0) * 64 + lane];
-                    const int fcnt = P.first_frame + f;
-                    const float n1 = (float)(fcnt - 1), n = (float)fcnt;
-                    prev.x = (prev.x * n1 + cur.x) / n;
-                    prev.y = (prev.y * n1 + cur.y) / n;
-                    prev.z = (prev.z * n1 + cur.z) / n;
-                    prev.w = 1.0f;
-                }
+                for (int f = f0; f < f1; f++) mean_step(prev, wslot[(f - f0) * 64 + lane], P.first_frame + f);
                 *px = prev;
             }
             if (chunk + 1 < P.n_chunks) publish_chunk(P, tile, chunk);
@@ -631,18 +618,21 @@ __global__ void __launch_bounds__(BLOCK, MINW) render_persistent_ab(const KP* __
 
 }  // namespace
 
+// The A/B structures, X(shape, LINK, LDSN, FAST): 512 threads, OPT 0, each with its stats twin.
+#define RT_AB_KERNELS(X)                                                           \
+    X(RT_SHAPE_FAST_LDS, false, true, true)                                        \
+    X(RT_SHAPE_FAST_GLOBAL, false, false, true)                                    \
+    X(RT_SHAPE_LINK_LDS, true, true, false)   /* one pixel per lane (variant 37) */ \
+    X(RT_SHAPE_META_LDS, false, true, false)                                       \
+    X(RT_SHAPE_META_GLOBAL, false, false, false)
+
 int rt_launch_render_ab(int shape, rt_kernel_args& a, const rt_kernel_args* d, size_t lds, bool stats, void* stream) {
     hipStream_t st = (hipStream_t)stream;
-#define RT_KERNEL(LINK, LDSN, BLOCK, FAST, OPT)                                                                     \
-    (stats ? launch_persistent(render_persistent_ab<LINK, 4, true, LDSN, BLOCK, FAST, OPT>, BLOCK, lds, a, d, st)  \
-           : launch_persistent(render_persistent_ab<LINK, 4, false, LDSN, BLOCK, FAST, OPT>, BLOCK, lds, a, d, st))
-    switch (shape) {
-        case RT_AB_SHAPE_FAST_LDS: return RT_KERNEL(false, true, 512, true, 0);
-        case RT_AB_SHAPE_FAST_GLOBAL: return RT_KERNEL(false, false, 512, true, 0);
-        case RT_AB_SHAPE_LINK_PIXEL: return RT_KERNEL(true, true, 512, false, 0);
-        case RT_AB_SHAPE_META_LDS: return RT_KERNEL(false, true, 512, false, 0);
-        case RT_AB_SHAPE_META_GLOBAL: return RT_KERNEL(false, false, 512, false, 0);
-        default: return -1;
-    }
-#undef RT_KERNEL
+#define RT_X(SHAPE, LINK, LDSN, FAST)                                                                             \
+    if (shape == SHAPE)                                                                                           \
+        return stats ? launch_persistent(render_persistent_ab<LINK, 4, true, LDSN, 512, FAST, 0>, 512, lds, a, d, st)  \
+                     : launch_persistent(render_persistent_ab<LINK, 4, false, LDSN, 512, FAST, 0>, 512, lds, a, d, st);
+    RT_AB_KERNELS(RT_X)
+#undef RT_X
+    return -1;
 }

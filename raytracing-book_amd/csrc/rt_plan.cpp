@@ -133,6 +133,102 @@ void plan_lds(const LdsIn& in, rt_kernel_args& a) {
                  (n_med == 0 || a.media_lds >= 0) && a.box_cmp_lds > a.sph_lds) ? 1 : 0;
 }
 
+// The release library has one kernel structure (tests/test_gpu_*.py pin it to the oracle):
+// pooled samples streamed over units with walks and shading in batches (render_stream) over
+// link-format nodes staged in LDS with the Perlin table, media, sphere and box records the
+// host placed after them (a.lds_end_f4), 4 waves per SIMD, as 2 x 512 or 1 x 1024 threads
+// per CU (a.block); when the nodes do not fit (a.lds_node_f4 < 2 n_nodes) the two-level
+// walk reads the nodes below the staged top levels from global memory (1024 threads).
+// Each in a shared-reciprocal division form (a.fastdiv) and the plain one.
+// The A/B library adds the other structures, all bit-identical (RT_OPTION_KERNEL_VARIANT):
+// 37 the link walk with one pixel per lane (the round-1 default), 30 threaded meta-word nodes
+// (LDS when they fit, else global), 61 the exact near-first stack walk, and the region-timer
+// stats twins 39 / 38 / 31 / 69.
+KernelPlan plan_kernel(rt_kernel_args& a, bool ab) {
+    KernelPlan k = {};
+    if (a.n_active <= 0) return k;   // the units divide by it (unit_geo); the caller skips an empty mask
+    int shape = RT_SHAPE_LINK_LDS;
+    size_t staged = (size_t)a.lds_end_f4 * 16;
+    bool stats = false, pool = true;
+    const bool tl = a.n_lnode_f4 > 0 && a.lds_node_f4 < 2 * a.n_nodes;
+    if (tl) shape = RT_SHAPE_LINK_TL;
+    if (ab) {
+        stats = a.variant == 38 || a.variant == 31 || a.variant == 69 || a.variant == 39;
+        pool = a.variant == 0 || a.variant == 39;
+        if (a.variant == 61 || a.variant == 69) {
+            const size_t stack_b = (size_t)RT_FAST_STACK * 512 * sizeof(short);
+            const size_t tree_b = (size_t)a.n_f2inner * 64 + (size_t)((a.n_f2leaves + 1) / 2) * 16;
+            shape = tree_b + stack_b <= RT_LDS_DYN_BYTES ? RT_SHAPE_FAST_LDS : RT_SHAPE_FAST_GLOBAL;
+            staged = shape == RT_SHAPE_FAST_LDS ? tree_b + stack_b : stack_b;
+        } else if (a.variant == 30 || a.variant == 31 || (!pool && tl)) {
+            // threaded meta-word nodes, then what the host placed after the link-format nodes
+            const size_t lds_t = (size_t)a.n_nodes * sizeof(rt_dnode);
+            staged = std::max(lds_t, staged);
+            shape = (lds_t <= RT_LDS_NODE_BYTES && staged <= RT_LDS_DYN_BYTES) ? RT_SHAPE_META_LDS : RT_SHAPE_META_GLOBAL;
+        }
+        if (shape == RT_SHAPE_FAST_LDS || shape == RT_SHAPE_FAST_GLOBAL || shape == RT_SHAPE_META_GLOBAL) {
+            if (shape == RT_SHAPE_META_GLOBAL) staged = 0;   // nothing else staged
+            a.perlin_lds = a.media_lds = a.sph_lds = a.box_cmp_lds = -1;
+            a.sph_mat_lds = a.box_mat_lds = a.tex_lds = -1;
+        }
+    }
+    const bool link = shape == RT_SHAPE_LINK_LDS || shape == RT_SHAPE_LINK_TL;
+    if (link && staged > (a.block == 1024 ? RT_LDS_BIG_BYTES : RT_LDS_DYN_BYTES)) return k;
+    if (shape == RT_SHAPE_LINK_TL && (a.block != 1024 || !pool)) return k;
+    if (pool && !a.samples && !a.wbuf) return k;   // pooled ordered / one-chunk units need the per-wave slots
+    // the leaf record prefetch reads only tables that are staged (the A/B shapes above may drop them)
+    a.leaf_pf = (a.leaf_pf && a.box_all_cmp && a.sph_lds >= 0 && a.box_cmp_lds > a.sph_lds &&
+                 (a.n_media == 0 || a.media_lds >= 0)) ? 1 : 0;
+    // the one-pixel-per-lane kernels (A/B) keep the lanes' running means in LDS after what is staged
+    a.acc_lds = (int)(staged / 16);
+    k.ok = true;
+    k.shape = shape;
+    k.stats = stats;
+    k.pool = pool;
+    k.lds = staged + (pool ? 0 : RT_LDS_ACC_BYTES);
+    k.block = 512;   // the A/B library's other structures: one instantiation per shape, OPT 0
+    const bool stream = pool && link;   // a RENDER_KERNELS entry
+    if (stream) {
+        // the default launch's configuration (RT_OPT_STD) holds: the kernels with it compiled in
+        const bool std_cfg = a.samples && a.sflags && a.media_sph &&
+                             (a.n_sph_lds == 0 || (a.sph_lds >= 0 && a.sph_mat_lds >= 0)) &&
+                             (a.n_media == 0 || a.media_lds >= 0) && (a.n_box_lds == 0 || a.box_cmp_lds >= 0) &&
+                             (!a.box_all_cmp || (a.leaf_pf && a.box_mat_lds >= 0)) && a.tex_lds >= 0;
+        const bool fd = a.fastdiv != 0, boxc = a.box_all_cmp != 0;
+        // a scene whose leaves are mostly sphere pairs (a.sph_pairs): without compact boxes, or
+        // (2: always) with them in the division regime; not the two-level kernels
+        const bool spair = shape == RT_SHAPE_LINK_LDS && ((a.sph_pairs && !boxc) || (a.sph_pairs == 2 && fd));
+        const bool std_k = std_cfg && fd && !(spair && boxc);
+        // the division-free box test: not the two-level kernel (SGPR spills), not the stats twins
+        const bool boxq = std_k && boxc && a.box_interior && shape == RT_SHAPE_LINK_LDS && !stats;
+        k.block = a.block == 1024 ? 1024 : 512;
+        k.opt = RT_OPT_SM_STREAM | (tl ? RT_OPT_TL : 0) | (fd ? RT_OPT_FD : 0) | (boxc ? RT_OPT_BOXC : 0) |
+                (spair ? RT_OPT_SPAIR : 0) | (std_k ? RT_OPT_STD : 0) | (boxq ? RT_OPT_BOXQ : 0) |
+                (a.tile_list ? RT_OPT_MASK : 0);
+    }
+    int* info = k.info;
+    info[RT_LI_SHAPE] = shape;
+    info[RT_LI_BLOCK] = link ? a.block : 512;
+    info[RT_LI_FASTDIV] = a.fastdiv;
+    info[RT_LI_PRETEST] = a.box_margin > 0.0f;
+    info[RT_LI_LDS] = (int)k.lds;
+    info[RT_LI_LDS_NODES] = link ? a.lds_node_f4 / 2 : 0;
+    info[RT_LI_COMPACT] = a.box_all_cmp + 2 * (a.box_cmp_lds >= 0);
+    info[RT_LI_STAGED] = a.samples != nullptr;
+    info[RT_LI_CHUNKS] = a.n_chunks;
+    info[RT_LI_SPINE] = pool ? a.spine_len : 0;
+    info[RT_LI_SPARSE] = a.samples && a.sflags ? 1 : 0;
+    // the report and the launch part ways here: the sphere-pair kernel runs whether or not the
+    // spheres are staged, and is reported only when they are (kept as it was)
+    info[RT_LI_SPAIR] = (k.opt & RT_OPT_SPAIR) && a.sph_lds >= 0 ? 1 : 0;
+    info[RT_LI_LEAF_PF] = stream ? a.leaf_pf : 0;
+    info[RT_LI_WALK_FRAC] = a.walk_frac;
+    info[RT_LI_TILES_ACTIVE] = a.n_active;
+    info[RT_LI_SHADE_LDS] = (a.sph_mat_lds >= 0) + 2 * (a.box_mat_lds >= 0) + 4 * (a.tex_lds >= 0);
+    info[RT_LI_BOXQ] = (k.opt & RT_OPT_BOXQ) ? 1 : 0;
+    return k;
+}
+
 // Frames per launch and the unit split.  Units = tiles x chunks; with too
 // few tiles per resident wave (small images, N-GPU stripes) the frames
 // are split into ordered chunks so the dynamic schedule has enough units

@@ -8,7 +8,93 @@
 
 #include "rt_device.h"
 
+// OPT bits of the render kernel template (rt_kernel.hip render_persistent<MINW, STATS, BLOCK, OPT>)
+#define RT_OPT_POOL 1   // pooled units (render_pool): without it a lane owns a pixel (variant 37)
+#define RT_OPT_SM 2     // with RT_OPT_POOL and the link walk: walks and shading in batches (render_stream)
+#define RT_OPT_FD 4     // with RT_OPT_SM: the scene is in the shared-reciprocal division regime (P.fastdiv)
+#define RT_OPT_STREAM 8 // with RT_OPT_SM: the wave streams over units (render_stream) instead of one at a time
+#define RT_OPT_TL 16    // with RT_OPT_STREAM: two-level walk (top levels in LDS, the rest of the nodes global)
+#define RT_OPT_BOXC 32  // with RT_OPT_STREAM: every box has a compact record (box_test_compact), no full box test
+#define RT_OPT_SPAIR 64 // with RT_OPT_STREAM: leaves of two spheres tested at once (leaf_prims_t; most leaves are)
+#define RT_OPT_BOXQ 256 // with RT_OPT_FD, RT_OPT_BOXC and RT_OPT_STD: the compact box test with one reciprocal per
+                        // axis and no division per face (box_test_compact_q; option box_interior)
+#define RT_OPT_MASK 512 // with RT_OPT_STREAM: the units run over the active tiles of a tile mask (P.tile_list, P.n_active;
+                        // rt_kernel.hip unit_geo); without it the code is the unmasked kernel's, unchanged
+#define RT_OPT_STD 128  // the default launch's configuration, compiled in (plan_kernel's std_cfg takes these
+                        // kernels when it holds): staged chunks with sparse staging (P.samples, P.sflags), every
+                        // medium bounded by a sphere (P.media_sph; no out-of-line boundary call), the leaf and
+                        // shading tables in LDS (spheres, media, box records, sphere materials, texture
+                        // descriptors) and with RT_OPT_BOXC the compact boxes' materials and the leaf record
+                        // prefetch (P.leaf_pf: the leaf stage holds only the prefetched forms).  Fewer wave-uniform
+                        // flags live through the rounds: the C3 kernel 128 -> 117 VGPRs, SGPR spills 34 -> 0
+// every release kernel streams pooled samples in batches
+#define RT_OPT_SM_STREAM (RT_OPT_POOL | RT_OPT_SM | RT_OPT_STREAM)
+
+// The instantiated render kernels, X(BLOCK, OPT): the link shape with everything in LDS as 2 x 512
+// or 1 x 1024 threads per CU, and the two-level walk (1024 only; no RT_OPT_SPAIR, and no RT_OPT_BOXQ:
+// SGPR spills), each over {plain, shared-reciprocal division} x {full, compact boxes} with the
+// RT_OPT_STD forms of the division kernels.  Every entry also has its twin for a launch under a tile
+// mask (OPT | RT_OPT_MASK), and in the A/B library its stats twin (STATS, OPT without RT_OPT_BOXQ).
+// rt_kernel.hip instantiates and dispatches from this list; plan_kernel chooses only from it
+// (tests/test_launch_plan.py: every entry is reachable and nothing else is chosen).
+#define RT_RENDER_KERNELS_LDS(X, BLOCK)                                                          \
+    X(BLOCK, RT_OPT_SM_STREAM)                                                                   \
+    X(BLOCK, RT_OPT_SM_STREAM | RT_OPT_BOXC)                                                     \
+    X(BLOCK, RT_OPT_SM_STREAM | RT_OPT_SPAIR)                                                    \
+    X(BLOCK, RT_OPT_SM_STREAM | RT_OPT_FD)                                                       \
+    X(BLOCK, RT_OPT_SM_STREAM | RT_OPT_FD | RT_OPT_STD)                                          \
+    X(BLOCK, RT_OPT_SM_STREAM | RT_OPT_FD | RT_OPT_SPAIR)                                        \
+    X(BLOCK, RT_OPT_SM_STREAM | RT_OPT_FD | RT_OPT_SPAIR | RT_OPT_STD)                           \
+    X(BLOCK, RT_OPT_SM_STREAM | RT_OPT_FD | RT_OPT_BOXC)                                         \
+    X(BLOCK, RT_OPT_SM_STREAM | RT_OPT_FD | RT_OPT_BOXC | RT_OPT_SPAIR)                          \
+    X(BLOCK, RT_OPT_SM_STREAM | RT_OPT_FD | RT_OPT_BOXC | RT_OPT_STD)                            \
+    X(BLOCK, RT_OPT_SM_STREAM | RT_OPT_FD | RT_OPT_BOXC | RT_OPT_STD | RT_OPT_BOXQ)
+#define RT_RENDER_KERNELS(X)                                                                     \
+    RT_RENDER_KERNELS_LDS(X, 512)                                                                \
+    RT_RENDER_KERNELS_LDS(X, 1024)                                                               \
+    X(1024, RT_OPT_SM_STREAM | RT_OPT_TL)                                                        \
+    X(1024, RT_OPT_SM_STREAM | RT_OPT_TL | RT_OPT_BOXC)                                          \
+    X(1024, RT_OPT_SM_STREAM | RT_OPT_TL | RT_OPT_FD)                                            \
+    X(1024, RT_OPT_SM_STREAM | RT_OPT_TL | RT_OPT_FD | RT_OPT_STD)                               \
+    X(1024, RT_OPT_SM_STREAM | RT_OPT_TL | RT_OPT_FD | RT_OPT_BOXC)                              \
+    X(1024, RT_OPT_SM_STREAM | RT_OPT_TL | RT_OPT_FD | RT_OPT_BOXC | RT_OPT_STD)
+
 namespace rt_impl __attribute__((visibility("hidden"))) {
+
+struct KernelId {
+    int block, opt;
+};
+// the release library's instantiations, mask twins included
+constexpr KernelId RENDER_KERNELS[] = {
+#define RT_X(BLOCK, OPT) {BLOCK, OPT}, {BLOCK, (OPT) | RT_OPT_MASK},
+    RT_RENDER_KERNELS(RT_X)
+#undef RT_X
+};
+constexpr int N_RENDER_KERNELS = (int)(sizeof(RENDER_KERNELS) / sizeof(RENDER_KERNELS[0]));
+
+// What one render launch runs (plan_kernel).
+struct KernelPlan {
+    bool ok;          // false: the launch is refused before anything is launched (nothing below is set)
+    int shape;        // RT_SHAPE_* (rt_device.h)
+    bool stats;       // the region-timer stats twin (A/B library)
+    bool pool;        // pooled samples (false: one pixel per lane, A/B library)
+    int block;        // workgroup size
+    int opt;          // the instantiation's OPT: a RENDER_KERNELS entry for the pooled link shapes (the
+                      // stats twins: without RT_OPT_BOXQ), 0 for the A/B library's other structures
+    size_t lds;       // dynamic LDS bytes
+    int info[RT_LI_N];   // rt_debug_last_launch's fields; those rt_render fills itself stay 0
+};
+// The launch decision of rt_launch_render: which kernel, with how much LDS, and what the launch
+// reports.  ab: the A/B library (its structures by a.variant; the release library ignores a.variant).
+// Reads of a: variant, block (512 or 1024, plan_lds), n_active, n_nodes, n_lnode_f4, lds_node_f4,
+// lds_end_f4, n_f2inner, n_f2leaves, fastdiv, box_all_cmp, box_interior, sph_pairs, leaf_pf, media_sph,
+// n_media, n_sph_lds, n_box_lds, the table offsets (perlin_lds, media_lds, sph_lds, box_cmp_lds,
+// sph_mat_lds, box_mat_lds, tex_lds), box_margin, n_chunks, spine_len, walk_frac, and whether
+// samples, sflags, wbuf and tile_list are null.
+// Writes to a: the table offsets = -1 for the A/B shapes that stage none of them (both near-first
+// shapes, global meta-word nodes), whether or not the launch is then refused; and, unless refused,
+// leaf_pf (cleared when a table the prefetch reads is not staged) and acc_lds.
+KernelPlan plan_kernel(rt_kernel_args& a, bool ab);
 
 struct LdsIn {
     int variant;

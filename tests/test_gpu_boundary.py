@@ -232,7 +232,7 @@ def test_chunk_chain_small_image(gpu, split):
     """Few tiles, many chunks: each of the 15 tiles' 600 frames in one-frame chunks over
     2 launches (300 + 300 frames): ordered, every chunk waits for the previous one (the
     hand-off is on the critical path; render_stream folds two units per wave in claim
-    order); staged, every chunk's colours folded by fold_kernel."""
+    order); staged, every chunk's colours folded after the launch (rt_moments.hip)."""
     s = rtamd.Scene(8, 40, 24, seed=1)
     ref = oracle_image(s, 600, spp=600)
     out = gpu_image(s, 600, spp=600, options=SPLITS[split])

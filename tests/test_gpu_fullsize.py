@@ -116,7 +116,7 @@ def test_exactness_shortcuts_change_no_bit_1080p(gpu, knob, sid):
 @pytest.mark.parametrize("sid", [8, 0, 6])
 def test_sparse_staging_changes_no_bit_1080p(gpu, sid, world, rank):
     """Sparse staging: every sample writes a flag byte and only the colours that are
-    not exactly zero their 16 bytes; fold_kernel reads a clear flag back as the zero colour.
+    not exactly zero their 16 bytes; the fold (rt_moments.hip) reads a clear flag back as the zero colour.
     Against dense staging, whole 1080p images of 16 frames continuing an
     accumulation (and one rank of 8 over 96 frames), the same bits; the default launch must
     have taken the sparse form."""

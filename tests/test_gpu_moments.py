@@ -37,7 +37,7 @@ def render(ctx, first, n):
 
 
 def replay(mean, m2, samples, first_frame):
-    """The recurrence of fold_moments_kernel in float32, one operation at a time."""
+    """The recurrence of the folds (rt_moments.hip mean_step, moment_step) in float32, one operation at a time."""
     mean, m2 = mean.astype(np.float32).copy(), m2.astype(np.float32).copy()
     with np.errstate(all="ignore"):
         for f in range(samples.shape[0]):
@@ -101,6 +101,76 @@ def test_moments_exact(gpu, sid, sparse):
         assert bit_equal(r["image"], mean), mismatch_report(r["image"], mean)
         assert bit_equal(r["m2"], m2), mismatch_report(r["m2"], m2)
     assert np.nanmax(runs[1]["m2"]) > 0.0
+
+
+FW, FH = 20, 12          # 3 x 2 tiles: partial ones at the right and at the bottom
+FOLD_MASK = (0, 2, 5)    # a full tile, a right-edge tile, the corner tile
+
+
+def fold_pattern(base):
+    """A distinct positive finite float per word (x * 0 is then +0, a zero image's)."""
+    return (np.uint32(base) + np.arange(FH * FW * 4, dtype=np.uint32)).view(np.float32).reshape(FH, FW, 4).copy()
+
+
+@functools.lru_cache(maxsize=None)
+def fold_run(n, sparse, masked, mom):
+    """Scene 6, frames 1..n over a pattern image (and pattern moments), under FOLD_MASK or no mask."""
+    ctx = context(rtamd.Scene(6, FW, FH, seed=SEED), 16, options=None if sparse else {"sparse_stage": 0})
+    if mom:
+        ctx.set_moments(True)
+    ctx.write_image(fold_pattern(0x3F800000))
+    if mom:
+        ctx.write_moments(fold_pattern(0x40000000), 5)
+    if masked:
+        mask = np.zeros(6, np.uint8)
+        mask[list(FOLD_MASK)] = 1
+        ctx.set_active_tiles(mask)
+    render(ctx, 1, n)
+    ctx.sync()
+    out = dict(launch=ctx.last_launch(), image=ctx.read_image(), m2=ctx.read_moments() if mom else None)
+    out["samples"] = ctx.read_samples() if out["launch"]["staged"] else None
+    ctx.close()
+    return out
+
+
+@pytest.mark.parametrize("masked", [False, True])
+@pytest.mark.parametrize("n", [1, 3, 8, 11])   # in place / the tail alone / one block of eight / a block and a tail
+def test_one_fold_body(gpu, n, masked):
+    """The staged folds (rt_moments.hip fold_pixel: per pixel or per active tile, mean alone or with the
+    moments, dense or sparse) against the numpy restatement of the staged colours, bit for bit; the image
+    bits do not depend on the moments or on sparse staging; a masked fold leaves every other word alone."""
+    px = np.zeros((FH, FW), bool)
+    for t in (FOLD_MASK if masked else range(6)):
+        px[(t // 3) * 8:(t // 3) * 8 + 8, (t % 3) * 8:(t % 3) * 8 + 8] = True
+    pat, pat2 = fold_pattern(0x3F800000), fold_pattern(0x40000000)
+    runs = {(sparse, mom): fold_run(n, sparse, masked, mom) for sparse in (False, True) for mom in (False, True)}
+    staged_runs = 0
+    for (sparse, mom), r in runs.items():
+        ll = r["launch"]
+        print(f"n {n} masked {masked} sparse {sparse} moments {mom}: {ll}")
+        assert ll["tiles_active"] == (3 if masked else 6)
+        if mom:
+            assert ll["staged"] == 1
+        assert not ll["staged"] or ll["sparse"] == (1 if sparse else 0)
+        if r["samples"] is not None:
+            staged_runs += 1
+            s = r["samples"]
+            assert s.shape == (n, FH, FW, 4)
+            mean, m2 = replay(pat, pat2, s, 1)
+            assert bit_equal(r["image"][px], mean[px]), mismatch_report(r["image"], np.where(px[..., None], mean, pat))
+            if mom:
+                assert bit_equal(r["m2"][px], m2[px])
+            if n >= 3:   # both kinds of colour: sparse staging stores the one and flags the other
+                zero = (s[..., :3].view(np.uint32) == 0).all(axis=-1)[:, px]
+                assert zero.any() and not zero.all()
+        assert np.array_equal(r["image"][~px].view(np.uint32), pat[~px].view(np.uint32))
+        if mom:
+            assert np.array_equal(r["m2"][~px].view(np.uint32), pat2[~px].view(np.uint32))
+    assert staged_runs >= 2
+    first = runs[(True, True)]["image"]
+    for key, r in runs.items():
+        assert bit_equal(r["image"], first), (key, mismatch_report(r["image"], first))
+    assert bit_equal(runs[(False, True)]["m2"], runs[(True, True)]["m2"])
 
 
 def test_moments_mean_what_they_say(gpu):

@@ -45,9 +45,9 @@ def merge(path):
     out = {}
     for row in csv.DictReader(open(path)):
         name = row["Name"]
-        if "dn_" not in name and "fold_moments" not in name:
+        if "dn_" not in name and "fold_moments" not in name and "fold_pixels" not in name:
             continue
-        short = next(k for k in ("dn_prologue_kernel", "dn_vb_kernel", "dn_filter_kernel", "fold_moments_kernel") if k in name)
+        short = next(k for k in ("dn_prologue_kernel", "dn_vb_kernel", "dn_filter_kernel", "fold_moments_kernel", "fold_pixels_kernel") if k in name)
         if "<" in name and short.startswith("dn_filter"):
             short += name[name.index("<"):name.index(">") + 1]   # <final>
         out[short] = {"calls": int(row["Calls"]), "avg_ms": round(float(row["AverageNs"]) * 1e-6, 5),

@@ -5,7 +5,7 @@ shape: scene 8, 1920x1080, 64 frames per step, depth 5 (bench.py preset c3).
 Three figures, each the median device time of a step (rt_last_render_ns: the render kernel and
 its fold) over --steps steps after --warmup:
   off      moments off (run twice, `off` and `off_again`, so the run-to-run spread is known)
-  on       moments on: every launch staged and folded by fold_moments_kernel
+  on       moments on: every launch staged and folded with the moments (fold_pixels_kernel<true>)
   noise    host time of one rt_noise() after a step (tile sums kernel + readback + the host sum)
 
     python tools/moments_cost.py [--out profiles/moments_cost.json]
