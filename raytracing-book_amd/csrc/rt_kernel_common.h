@@ -165,6 +165,13 @@ __device__ __forceinline__ float rnd(float& rf, float px, float py) {
     return g_fract(g_sin(g_dot2(co, k)) * 43758.5453123f);
 }
 
+// The trimmed scene-8 kernels (the RT_OPT_BOXQ instantiations, DESIGN §4 "Walk trim"): the leaf stage
+// computes a slot record's LDS address by selects instead of a branch cascade (leaf_prims_t).
+// tools/build_variant_lib.sh builds the other form (-DRT_WT_DISPATCH=0) for tools/lib_ab.py.
+#ifndef RT_WT_DISPATCH
+#define RT_WT_DISPATCH 1
+#endif
+
 // Source of hit_record.uv (compute.glsl:62): the last successful sphere or quad
 // hit of the sample (it persists across bounces; media do not write it).
 struct UvSrc {
@@ -693,7 +700,8 @@ __device__ __forceinline__ bool aabb_pk(float4 n0, float4 n1, v3 o, v3 inv, floa
 
 // The two prims of a leaf (compute.glsl:247-256), left then right.
 // FD: the shared-reciprocal divisions (rcp_nr / div_nr; FD kernels only).
-// BOXQ (RT_OPT_BOXQ, with FD, BOXC and STD): the compact box test as box_test_compact_q.
+// BOXQ (RT_OPT_BOXQ, with FD, BOXC and STD): the compact box test as box_test_compact_q, and the
+// prefetched slot record's address by selects (RT_WT_DISPATCH).
 template <bool STATS, bool FD, bool BOXC = false, bool SPAIR = false, bool STD = false, bool BOXQ = false>
 __device__ __forceinline__ void leaf_prims_t(const KP& P, uint32_t meta, uint32_t prims, v3 o, v3 d, v3 inv, float a,
                                              float time, float tmin, float& tmax, float& rf, float px, float py, Hit& h,
@@ -777,7 +785,23 @@ __device__ __forceinline__ void leaf_prims_t(const KP& P, uint32_t meta, uint32_
         // STD kernels (RT_OPT_STD): known on, the other forms compiled out
         const bool pf = BOXC && (STD || P.leaf_pf);   // wave-uniform
         float4 q0, q1, q2;
-        if (pf) {
+        if (pf && RT_WT_DISPATCH && BOXQ && !STATS) {
+            // The same address without the branch cascade the nested form below compiles to (each arm
+            // reads its table's offset from the argument block, a load the compiler may not hoist
+            // over the type test): the three offsets are read first -- wave-uniform, scalar -- as
+            // (table byte address | record bytes << 18), one word is selected per lane and the
+            // address is one multiply-add.  LDS ends below 2^18 bytes; a quad or an empty slot
+            // selects 0 and reads node 0 as before.
+            const uint32_t ws = ((uint32_t)P.sph_lds << 4) | (32u << 18);
+            const uint32_t wb = ((uint32_t)P.box_cmp_lds << 4) | ((16u * RT_BOXC_F4) << 18);
+            const uint32_t wm = ((uint32_t)P.media_lds << 4) | (48u << 18);
+            const uint32_t w = ty == RT_MODEL_SPHERE ? ws : ty == RT_MODEL_BOX ? wb : ty == RT_MODEL_CONSTANT_MEDIUM ? wm : 0u;
+            const float4* r = reinterpret_cast<const float4*>(reinterpret_cast<const char*>(rt_dyn_lds) +
+                                                              ((w >> 18) * (uint32_t)ix + (w & 0x3FFFFu)));
+            q0 = r[0];
+            q1 = r[1];
+            q2 = r[2];
+        } else if (pf) {
             const int off = ty == RT_MODEL_SPHERE ? P.sph_lds + 2 * ix
                           : ty == RT_MODEL_BOX ? P.box_cmp_lds + RT_BOXC_F4 * ix
                           : ty == RT_MODEL_CONSTANT_MEDIUM ? P.media_lds + 3 * ix : 0;

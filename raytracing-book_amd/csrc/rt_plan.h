@@ -17,7 +17,8 @@
 #define RT_OPT_BOXC 32  // with RT_OPT_STREAM: every box has a compact record (box_test_compact), no full box test
 #define RT_OPT_SPAIR 64 // with RT_OPT_STREAM: leaves of two spheres tested at once (leaf_prims_t; most leaves are)
 #define RT_OPT_BOXQ 256 // with RT_OPT_FD, RT_OPT_BOXC and RT_OPT_STD: the compact box test with one reciprocal per
-                        // axis and no division per face (box_test_compact_q; option box_interior)
+                        // axis and no division per face (box_test_compact_q; option box_interior), and the leaf
+                        // stage's prefetched record address by selects (rt_kernel_common.h RT_WT_DISPATCH)
 #define RT_OPT_MASK 512 // with RT_OPT_STREAM: the units run over the active tiles of a tile mask (P.tile_list, P.n_active;
                         // rt_kernel.hip unit_geo); without it the code is the unmasked kernel's, unchanged
 #define RT_OPT_STD 128  // the default launch's configuration, compiled in (plan_kernel's std_cfg takes these
