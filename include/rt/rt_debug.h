@@ -174,6 +174,10 @@ enum {
                                            planes from one reciprocal per axis, its faces
                                            accepted without dividing, alpha / beta divided
                                            once for the accepted face (1)                   */
+    RT_OPTION_FIRST_LEAF = 29,          /* the same kernels: when the spine ends at its leaf, a
+                                           walk that starts past the spine tests that leaf
+                                           where it begins, from a wave-uniform record, before
+                                           its first round (rt_debug_first_leaf) (1)        */
     RT_OPTION_KERNEL_VARIANT = 100,     /* A/B build: 0, 37, 30, 61 (+ stats twins)         */
     RT_OPTION_DEBUG_FLAGS = 101         /* A/B build: ablations, NOT exact                  */
 };
@@ -201,6 +205,15 @@ int rt_debug_get_option(struct rt_ctx* ctx, int option, int* value);
  *           tile without one; 0 when the render launched nothing because no tile was active
  * n <= 21 ints are written; returns RT_ERR_STATE before the first render. */
 int rt_debug_last_launch(struct rt_ctx* ctx, int* out, int n);
+
+/* The first-leaf prologue of the last rt_render on the context's first device (option first_leaf):
+ *   out[0] 1 when it was armed -- the option on, the spine on and ending at its leaf, and a kernel
+ *          that holds the prologue (out[19] of rt_debug_last_launch) -- else 0, and the rest 0
+ *   out[1] the leaf's link (the spine's start: sign bit | leaf ordinal)
+ *   out[2] the leaf record's type byte (slot 0's type in bits 0-3, slot 1's in bits 4-7)
+ *   out[3] its prim word (slot 0's index in bits 0-15, slot 1's in bits 16-31)
+ * Returns RT_ERR_STATE before the first render. */
+int rt_debug_first_leaf(struct rt_ctx* ctx, int out[4]);
 
 /* Host-only: the launch decision of a render (which kernel instantiation, with how much LDS, and
  * the rt_debug_last_launch fields it reports) for the deciding inputs in[RT_PK_*] -- the launch's

@@ -616,7 +616,24 @@ int rt_render(rt_ctx* c, int first_frame, int n_frames, const float* rand_factor
     a.box_vnodes = c->walk_v && c->n_vnodes > 0 ? 1 : 0;
     a.n_nodes = c->n_walk_nodes;
     a.n_lnode_f4 = (int)c->walk_links.size();
-    plan_spine(c->walk_links, c->n_walk_nodes, c->cam, c->spine, a);
+    // (a chain that ends at its leaf counts at any length where the kernel may hold the first-leaf
+    // prologue: the compact-box kernels with the division-free box test, rt_plan.cpp)
+    const size_t nb_all = c->host_buf[RT_BIND_BOXES].size() / sizeof(rt_box);
+    const bool leaf_chain = c->first_leaf && c->box_interior && c->compact_boxes && nb_all > 0 &&
+                            c->n_boxc_ok == (int)nb_all && (c->variant == 0 || c->variant == 39);
+    plan_spine(c->walk_links, c->n_walk_nodes, c->cam, c->spine, leaf_chain, a);
+    // the first-leaf prologue (rt_kernel.hip render_stream; option first_leaf): armed when the spine is
+    // on and ends at the chain's leaf; the kernel gets that leaf's record as the walk's leaf stage reads it
+    if (c->first_leaf && a.spine_len > 0 && (a.spine_start & RT_LINK_LEAF) && a.spine_start != RT_LINK_END) {
+        const size_t ord = a.spine_start & 0x7FFFFFFFu, nf4 = 2 * (size_t)c->n_walk_nodes;
+        if (nf4 + ord / 2 < c->walk_links.size()) {
+            uint32_t w[4];
+            std::memcpy(w, &c->walk_links[nf4 + ord / 2], 16);
+            a.first_leaf[0] = 1u;
+            a.first_leaf[1] = w[2 * (ord & 1)];
+            a.first_leaf[2] = w[2 * (ord & 1) + 1];
+        }
+    }
     const bool pooled = c->variant == 0 || c->variant == 39;
     const int n_sph = (int)(c->host_buf[RT_BIND_SPHERES].size() / sizeof(rt_sphere));
     const int n_box = (int)(c->host_buf[RT_BIND_BOXES].size() / sizeof(rt_box));
@@ -798,6 +815,12 @@ int rt_render(rt_ctx* c, int first_frame, int n_frames, const float* rand_factor
                 c->last_launch[RT_LI_VNODES] = a.box_vnodes ? c->n_vnodes : 0;
                 c->last_launch[RT_LI_COLLAPSED] = c->walk_c ? c->n_dropped : 0;
                 c->last_launch[RT_LI_REBUILT] = c->n_rebuilt > 0 ? 1 : 0;
+                // (rt_debug_first_leaf) the prologue is compiled into the RT_OPT_BOXQ kernels alone
+                const bool fl = a.first_leaf[0] != 0 && c->last_launch[RT_LI_BOXQ] != 0;
+                c->first_leaf_last[0] = fl ? 1 : 0;
+                c->first_leaf_last[1] = fl ? (int)a.spine_start : 0;
+                c->first_leaf_last[2] = fl ? (int)(a.first_leaf[1] & 0xFFu) : 0;
+                c->first_leaf_last[3] = fl ? (int)a.first_leaf[2] : 0;
             }
         }
         HIPCHK(c, hipEventRecord(d.ev_stop, d.stream));

@@ -104,6 +104,9 @@ struct rt_ctx {
     bool box_vnodes = true;         // option box_vnodes
     bool box_interior = true;       // option box_interior
     bool zero_dir_end = true;       // option zero_dir_end (rt_kernel.hip render_stream)
+    bool first_leaf = true;         // option first_leaf: a walk that starts at the spine's leaf tests it where
+                                    // it begins (rt_kernel.hip render_stream; the RT_OPT_BOXQ kernels)
+    int first_leaf_last[4] = {0};   // rt_debug_first_leaf: the last launch's (armed, leaf link, type byte, prims)
     bool collapse = true;           // option collapse: the walk leaves out inner nodes (plan_collapse)
     int rebuild = 2;                // option rebuild: the walk's inner nodes rebuilt over its leaves (rebuild_inner mode)
     bool walk_r = false;            // walk_links were built on the rebuilt inner nodes

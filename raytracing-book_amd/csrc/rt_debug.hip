@@ -215,6 +215,7 @@ int rt_debug_set_option(rt_ctx* c, int option, int v) {
         case RT_OPTION_BOX_VNODES: c->box_vnodes = v != 0; break;
         case RT_OPTION_BOX_INTERIOR: c->box_interior = v != 0; break;
         case RT_OPTION_ZERO_DIR_END: c->zero_dir_end = v != 0; break;
+        case RT_OPTION_FIRST_LEAF: c->first_leaf = v != 0; break;
         case RT_OPTION_COLLAPSE: c->collapse = v != 0; break;
         case RT_OPTION_REBUILD: if (v < 0 || v > 2) return bad(); c->rebuild = v; break;
         case RT_OPTION_CHUNK_TARGET: if (v < 0) return bad(); c->chunk_target = v; break;
@@ -258,6 +259,7 @@ int rt_debug_get_option(rt_ctx* c, int option, int* v) {
         case RT_OPTION_BOX_VNODES: *v = c->box_vnodes; break;
         case RT_OPTION_BOX_INTERIOR: *v = c->box_interior; break;
         case RT_OPTION_ZERO_DIR_END: *v = c->zero_dir_end; break;
+        case RT_OPTION_FIRST_LEAF: *v = c->first_leaf; break;
         case RT_OPTION_COLLAPSE: *v = c->collapse; break;
         case RT_OPTION_REBUILD: *v = c->rebuild; break;
         case RT_OPTION_CHUNK_TARGET: *v = c->chunk_target; break;
@@ -296,6 +298,13 @@ int rt_debug_last_launch(rt_ctx* c, int* out, int n) {
     if (!c || !out || n < 0 || n > RT_LI_N) return RT_ERR_INVALID_ARG;
     if (!c->launched) return set_err(c, RT_ERR_STATE, "no render launched yet");
     std::memcpy(out, c->last_launch, sizeof(int) * (size_t)n);
+    return RT_OK;
+}
+
+int rt_debug_first_leaf(rt_ctx* c, int out[4]) {
+    if (!c || !out) return RT_ERR_INVALID_ARG;
+    if (!c->launched) return set_err(c, RT_ERR_STATE, "no render launched yet");
+    std::memcpy(out, c->first_leaf_last, sizeof(c->first_leaf_last));
     return RT_OK;
 }
 

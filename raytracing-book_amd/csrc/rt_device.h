@@ -207,6 +207,11 @@ struct rt_kernel_args {
     int spine_len;
     uint32_t spine_start;
     float spine_lo[3], spine_hi[3];   // the boxes' intersection, shrunk by 2^-18 of its largest coordinate
+    // the first-leaf prologue (rt_kernel.hip render_stream; option first_leaf): the spine reaches down
+    // to the chain's leaf (spine_start is a leaf link), so a walk that starts past the spine starts at
+    // that leaf and tests it where the walk begins.  first_leaf[0] 1/0: armed; [1], [2]: the leaf's
+    // record (types | next << 8, prims), the words the walk's leaf stage would read
+    uint32_t first_leaf[3];
     // bounds of the device-side waits, in ticks of the 100 MHz real-time clock (s_memrealtime)
     unsigned long long watchdog_ticks;     // render_stream: no sample stored by the wave for this long
                                            // -> fault word 2, the wave leaves (checked on its first pass

@@ -330,6 +330,29 @@ __device__ __forceinline__ void render_stream(const KP& P, const float4* __restr
                 const unsigned long long m = __ballot(status == RT_SM_TRACE && nx == 0u);
                 if (m && first_active_lane()) atomicAdd(&P.node_hits[P.n_nodes], (unsigned)__popcll(m));
             }
+            // The first-leaf prologue (the RT_OPT_BOXQ kernels; P.first_leaf: the spine ends at the
+            // chain's leaf, so spine_start is that leaf's link).  A new walk that starts past the spine
+            // holds that leaf before its first node step: the first round would find the lane parked
+            // (two node steps re-reading node 0 for the wave), run the generic leaf stage for a leaf
+            // every such lane shares, and only the next round would walk.  Here the lane tests the leaf
+            // at once.  The same values: these are the lane's first two tests of the walk either way,
+            // with ray_t.max infinite and no hit yet, the same leaf_prims_t with the same record words
+            // (the host's copy of the words the leaf stage reads from LDS), a medium's rnd() is the
+            // walk's first draw either way, and the lane goes on at the leaf's skip node exactly as
+            // after a round's leaf stage.  Only the place in the pass where the tests run moves.  The
+            // record is wave-uniform (scalar loads), so the slots' type tests are scalar branches and no
+            // lane reads a leaf record.  A lane that starts at the root (origin outside the spine box,
+            // non-finite origin or direction) is not touched.
+            if constexpr (RT_WT_FIRST_LEAF && (OPT & RT_OPT_BOXQ) != 0 && !STATS) {
+                if (P.first_leaf[0] && status == RT_SM_TRACE && nx == P.spine_start) {
+                    const uint32_t lx = P.first_leaf[1], ly = P.first_leaf[2];
+                    leaf_prims_t<STATS, FD, BOXC, (OPT & RT_OPT_SPAIR) != 0, STD, true>(P, lx << 16, ly, S.o, S.d, inv, a,
+                                                                                        S.time, 0.001f, tmax, S.rf, fx, fy,
+                                                                                        h, has, st);
+                    nx = lx >> 8;   // the leaf's skip node
+                    if (nx == RT_LINK_NEXT_END) status = RT_SM_HIT;
+                }
+            }
         }
         // rounds of node walk + leaf tests (trace()), at wave priority 1: their dependent LDS
         // chains then issue as soon as their data is back, and the shading's long VALU runs (at

@@ -171,6 +171,11 @@ __device__ __forceinline__ float rnd(float& rf, float px, float py) {
 #ifndef RT_WT_DISPATCH
 #define RT_WT_DISPATCH 1
 #endif
+// The same kernels' first-leaf prologue (rt_kernel.hip render_stream, DESIGN §4 "First leaf"): a walk
+// that starts at the spine's leaf tests it where the walk begins.  -DRT_WT_FIRST_LEAF=0: compiled out.
+#ifndef RT_WT_FIRST_LEAF
+#define RT_WT_FIRST_LEAF 1
+#endif
 
 // Source of hit_record.uv (compute.glsl:62): the last successful sphere or quad
 // hit of the sample (it persists across bounces; media do not write it).

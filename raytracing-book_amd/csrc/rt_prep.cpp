@@ -519,7 +519,12 @@ int tail_chunks_for(int n_nodes) { return n_nodes > 1024 ? 1 : 0; }
 // scene 8's ~41 node steps per walk).  Picks the longest prefix of the chain whose boxes'
 // intersection holds the camera and >= 3/4 of the leaf boxes' centres (where later walks
 // start), at least 3 nodes; its last node's hit successor is where such a walk starts.
-void plan_spine(const std::vector<float4>& L, int n_nodes, const rt_camera_ubo& cam, bool on,
+// leaf_chain (the first-leaf prologue, rt_kernel.hip render_stream): a prefix that ends at the chain's
+// leaf counts from one node on.  The rebuilt tree (rebuild_inner) splits scene 8's fog leaf off at the
+// root, so its chain is two nodes -- too short to pay for the entry test by the node steps it
+// saves, but with the prologue the walk also leaves out its first round's parked steps and the generic
+// leaf stage for that leaf.  The entry's argument holds for any length.
+void plan_spine(const std::vector<float4>& L, int n_nodes, const rt_camera_ubo& cam, bool on, bool leaf_chain,
                 rt_kernel_args& a) {
     a.spine_len = 0;
     a.spine_start = 0;
@@ -570,7 +575,7 @@ void plan_spine(const std::vector<float4>& L, int n_nodes, const rt_camera_ubo& 
                   cx[3 * j + 2] > slo[2] && cx[3 * j + 2] < shi[2];
         if (4 * in < 3 * n_leaf) break;
         const uint32_t hit = bits(b1.z);
-        if (len >= 3) {
+        if (len >= 3 || (leaf_chain && (hit & RT_LINK_LEAF) != 0 && hit != RT_LINK_END)) {
             a.spine_len = len;
             a.spine_start = hit;
             for (int k = 0; k < 3; k++) {

@@ -57,7 +57,8 @@ std::vector<uint8_t> plan_collapse(const std::vector<rt_dnode>& dn, const rt_cam
 std::vector<uint8_t> plan_from_hits(const std::vector<rt_dnode>& dn, const std::vector<int64_t>& H, int64_t walks);
 int walk_frac_for(int n_nodes);
 int tail_chunks_for(int n_nodes);
-void plan_spine(const std::vector<float4>& L, int n_nodes, const rt_camera_ubo& cam, bool on, rt_kernel_args& a);
+void plan_spine(const std::vector<float4>& L, int n_nodes, const rt_camera_ubo& cam, bool on, bool leaf_chain,
+                rt_kernel_args& a);
 int pair_leaves_permille(const std::vector<float4>& L, int n_nodes);
 FastTables build_fast(const std::vector<rt_dnode>& dn, size_t ns, const rt_quad* quads, size_t nq, const rt_box* boxes,
                       size_t nb);

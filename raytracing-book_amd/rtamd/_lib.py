@@ -164,6 +164,8 @@ def _amd_protos(L, old_rev=False):
     _proto(L, "rt_debug_last_launch", i, vp, c_int_p, i)
     if not old_rev or hasattr(L, "rt_debug_plan_kernel"):   # ... or from before the host-side launch plan
         _proto(L, "rt_debug_plan_kernel", i, c_int_p, i, i, c_int_p, i, c_int_p, c_int_p, i, c_int_p)
+    if not old_rev or hasattr(L, "rt_debug_first_leaf"):   # ... or from before the first-leaf prologue
+        _proto(L, "rt_debug_first_leaf", i, vp, c_int_p)
     _proto(L, "rt_set_bvh_mode", i, vp, i)
     _proto(L, "rt_debug_walk_bvh", i, vp, vp, sz, ctypes.POINTER(sz))
     _proto(L, "rt_debug_build_sah_bvh", i, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, i, c_float_p, f, vp, sz,

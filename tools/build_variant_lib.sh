@@ -2,6 +2,8 @@
 # Builds raytracing-book_amd/lib/<tag>/librtamd.so from the working tree's kernel source with extra
 # compiler definitions (ablations and A/B forms, e.g. -DRT_ABL_UNITVEC1) and the working tree's
 # C ABI object, for tools/lib_ab.py.  usage: tools/build_variant_lib.sh <tag> <-Dflags...>
+# The scene-8 kernels' other forms (rt_kernel_common.h): -DRT_WT_DISPATCH=0 the leaf stage's record
+# address by a branch cascade, -DRT_WT_FIRST_LEAF=0 without the first-leaf prologue.
 set -e
 TAG=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)
