@@ -176,6 +176,12 @@ __device__ __forceinline__ float rnd(float& rf, float px, float py) {
 #ifndef RT_WT_FIRST_LEAF
 #define RT_WT_FIRST_LEAF 1
 #endif
+// The same kernels' per-pass trims (DESIGN §4 "Per-pass blocks"): the code a wave runs once per pass.
+// RT_PB_NOLIGHT: shade()'s mixture without the lights_random call when no light is registered.
+// -DRT_PB_NOLIGHT=0: the mixture as every other kernel has it.
+#ifndef RT_PB_NOLIGHT
+#define RT_PB_NOLIGHT 1
+#endif
 
 // Source of hit_record.uv (compute.glsl:62): the last successful sphere or quad
 // hit of the sample (it persists across bounces; media do not write it).
@@ -1413,7 +1419,8 @@ struct Path {
 // Returns true when the path ended, with its color in `result`.
 // STD (RT_OPT_STD kernels): the shading tables are staged -- every sphere's, and with PK_INLINE (the
 // compact-box kernels) every box's; the texture descriptors
-template <bool PK_INLINE = false, bool STATS = false, bool STD = false>
+// PB (the RT_OPT_BOXQ kernels): the per-pass trims (RT_PB_*, DESIGN §4 "Per-pass blocks").
+template <bool PK_INLINE = false, bool STATS = false, bool STD = false, bool PB = false>
 __device__ __forceinline__ bool shade(const KP& P, Path& S, const Hit& h, float px, float py, v3& result,
                                       unsigned long long* st = nullptr) {
     unsigned long long c0 = STATS ? clock64() : 0;
@@ -1556,6 +1563,72 @@ __device__ __forceinline__ bool shade(const KP& P, Path& S, const Hit& h, float 
         if (STATS) st_add(st, ST_SH_TEX_CYC, clock64() - c0);
         return false;
     }
+    // The RT_OPT_BOXQ kernels (PB, RT_PB_NOLIGHT): the mixture (compute.glsl:322-337) with a branch for a
+    // launch without lights; a launch with lights takes the other branch, the code below this block
+    // with the same operations, and both share one texture_color.  Every other kernel compiles the code
+    // below alone, as it was.  (PB kernels have no stats twin.)
+    if constexpr (PB && RT_PB_NOLIGHT) {
+        float spdf, rpdf;   // rpdf: the reciprocal divs3 takes of the mixture pdf
+        if (P.lights_count == 0) {
+            // No registered light (a wave-uniform scalar branch; scene 8).  lights_random returns vec3(0)
+            // whatever it draws (li >= lights_count = 0), so a lane whose mixture draw
+            // is below 0.5 gets d = vec3(0) without the call.  The call's own rnd() only advanced rf, and
+            // that rf is never read again:
+            //   * a Lambertian lane has cs = dot(vec3(0), normal), which is 0 (NaN for a non-finite
+            //     normal): not in (0, inf), so mpdf = 0, pdf = 0.5*0 + 0.5*0 = 0 and the path ends here
+            //     with acc x emis;
+            //   * an isotropic lane goes on along vec3(0): that bounce hits nothing and draws no rand()
+            //     (bounce(), compute.glsl:226-229; taken at once under zero_dir_end, one pass later
+            //     without it), and its miss ends the path;
+            //   * metal and dielectric lanes (skip_pdf) returned above;
+            //   * the lane's next sample re-seeds rf in start_path.
+            // lights_pdf_value is 0 for any d, so the mixture pdf is one of two constants, written in the
+            // parent's operations (the compiler folds them as the hardware evaluates them: correctly
+            // rounded), and so is the reciprocal divs3 takes of it.
+            if (rnd(rf, px, py) < 0.5f) d = mk3s(0.0f);
+            if (mid == RT_MAT_LAMBERTIAN) {
+                const float cs = g_dot(d, normal);
+                if (!(cs > 0.0f && cs < INFINITY)) {   // mpdf = 0: pdf == 0
+                    result = mul3(S.acc, emis);
+                    return true;
+                }
+                spdf = g_max(0.0f, g_dot(normal, g_normalize(d)) / RT_PI);
+                rpdf = 1.0f / (0.5f * 0.0f + 0.5f * (1.0f / RT_PI));
+            } else if (mid == RT_MAT_ISOTROPIC) {
+                spdf = 1.0f / (4.0f * RT_PI);
+                rpdf = 1.0f / (0.5f * 0.0f + 0.5f * (1.0f / (4.0f * RT_PI)));
+            } else {   // (no other material reaches the mixture) mpdf = 0: pdf == 0
+                result = mul3(S.acc, emis);
+                return true;
+            }
+        } else {
+            if (rnd(rf, px, py) < 0.5f) d = lights_random(P, p, rf, px, py);
+            float lpdf = (P.lights_count > 0) ? lights_pdf_value(P, p, d, S.time) : 0.0f;
+            float mpdf;
+            // cosine_pdf_value (pdf.glsl:32-35): max(0, normalize(cos)/PI) with the scalar
+            // normalize = cos/|cos| in {+1, -1, NaN}: 1/PI exactly when 0 < cos < inf, else 0
+            if (mid == RT_MAT_LAMBERTIAN) {
+                float cs = g_dot(d, normal);
+                mpdf = (cs > 0.0f && cs < INFINITY) ? 1.0f / RT_PI : 0.0f;
+            }
+            else if (mid == RT_MAT_ISOTROPIC) mpdf = 1.0f / (4.0f * RT_PI);
+            else mpdf = 0.0f;
+            float pdf = 0.5f * lpdf + 0.5f * mpdf;
+            if (pdf == 0.0f) {
+                result = mul3(S.acc, emis);
+                return true;
+            }
+            if (mid == RT_MAT_LAMBERTIAN) spdf = g_max(0.0f, g_dot(normal, g_normalize(d)) / RT_PI);
+            else if (mid == RT_MAT_ISOTROPIC) spdf = 1.0f / (4.0f * RT_PI);
+            else spdf = 0.0f;
+            rpdf = 1.0f / pdf;
+        }
+        v3 att = solid_tex ? mk3(sc[0], sc[1], sc[2]) : texture_color<PK_INLINE, STD>(P, p, tex_id, S.uvs, S.time);
+        const v3 as = scale3(att, spdf);
+        S.acc = mul3(S.acc, mk3(as.x * rpdf, as.y * rpdf, as.z * rpdf));   // divs3(as, pdf)
+        S.d = d;
+        return false;
+    }
     if (rnd(rf, px, py) < 0.5f) d = lights_random(P, p, rf, px, py);
     float lpdf = (P.lights_count > 0) ? lights_pdf_value(P, p, d, S.time) : 0.0f;
     float mpdf;
@@ -1590,7 +1663,7 @@ __device__ __forceinline__ bool shade(const KP& P, Path& S, const Hit& h, float 
 
 // The rest of ray_color's loop body after the walk (compute.glsl:308-340): the
 // uv the walk left (compute.glsl:62), the background on a miss, else shade().
-template <bool PK_INLINE = false, bool STATS = false, bool STD = false>
+template <bool PK_INLINE = false, bool STATS = false, bool STD = false, bool PB = false>
 __device__ __forceinline__ bool after_trace(const KP& P, Path& S, const Hit& h, bool hit, float px, float py,
                                             v3& result, unsigned long long* st = nullptr) {
     if (h.uv_kind_idx != 0) {
@@ -1605,7 +1678,7 @@ __device__ __forceinline__ bool after_trace(const KP& P, Path& S, const Hit& h, 
         result = mul3(S.acc, mk3(P.background[0], P.background[1], P.background[2]));
         return true;
     }
-    return shade<PK_INLINE, STATS, STD>(P, S, h, px, py, result, st);
+    return shade<PK_INLINE, STATS, STD, PB>(P, S, h, px, py, result, st);
 }
 
 // Camera ray of frame `frame_count` (compute.glsl:345-350, random.glsl:19-30,82-100).
