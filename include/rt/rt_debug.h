@@ -253,6 +253,65 @@ enum {
 int rt_debug_plan_kernel(const int* in, int n_in, int ab, int* out, int n_out, int* info, int* table, int table_cap,
                          int* n_table);
 
+/* Host-only: what rt_render would assemble for a scene and launch first, with no context and no
+ * device: the uploads' host halves, validation, the walk's trees, the scene's kernel arguments, the
+ * unit split and the frame counts, by the functions rt_render itself runs (csrc/rt_args.h).
+ * In: the six bindings as for rt_upload_buffer (all six count as uploaded), textures as for
+ * rt_upload_texture (tex_w[slot] = 0: none), the camera UBO, rt_set_params' values, the image size
+ * and partition, n_options (option, value) pairs as for rt_debug_set_option (ab = 1: the A/B
+ * library's options >= 100 too, RT_OPTION_KERNEL_VARIANT among them), rt_set_bvh_mode's mode,
+ * rt_set_moments' switch, a tile mask as its n_mask ascending tile indices (n_mask < 0: no mask), the
+ * frame counts before the call (prev_frames for every tile, or prev_tile_frames, one per tile of the
+ * rank's stripe), rt_render's first_frame and n_frames, and the two numbers rt_render asks the device
+ * for: its resident waves and its free bytes.
+ * Out: pk, the RT_PK_* inputs of the first launch (feed them to rt_debug_plan_kernel); launched, 0
+ * when the call launches nothing (an empty mask, no frame, no row) and pk is all 0; the
+ * rt_debug_last_launch fields rt_render fills itself; rt_debug_first_leaf's words (by the kernel
+ * rt_debug_plan_kernel chooses for pk) and the prologue's argument words; plan_split's and the
+ * first launch's plan_chunks' results; the frame counts after the call (frames_all; n_tile_frames
+ * counts written to tile_frames when the tiles differ, else 0; RT_ERR_LIMIT if tile_cap is short).
+ * Optional (NULL: not wanted): links / links_cap gets the walk's link array (links_f4 float4), args /
+ * args_cap the first launch's rt_kernel_args block (args_bytes; csrc/rt_device.h) with every pointer
+ * and the rand factors zeroed.  Returns what the upload, rt_render or option call it mirrors would. */
+typedef struct rt_debug_scene_in {
+    const void* buf[6];
+    size_t buf_bytes[6];
+    int tex_format[8], tex_w[8], tex_h[8];
+    const void* tex[8];
+    const float* camera;   /* 28 floats */
+    int max_depth;
+    float background[3], sqrt_spp, recip_sqrt_spp;
+    int width, height, rank, world, stripe_rows;
+    const int* options;
+    int n_options;
+    int ab, bvh_mode, moments;
+    const int* mask;
+    int n_mask;
+    int prev_frames;
+    const int* prev_tile_frames;
+    int first_frame, n_frames;
+    long long waves;
+    size_t free_bytes;
+} rt_debug_scene_in;
+typedef struct rt_debug_scene_out {
+    int pk[RT_PK_N];
+    int launched;
+    int bvh_mode, vnodes, collapsed, rebuilt;
+    int first_leaf[4];
+    unsigned int first_leaf_args[3], spine_start;
+    int per_launch, chunks_wanted, staged;
+    int n_chunks, chunk_frames, tail_chunks, stage;
+    int frames_all, n_tile_frames;
+    int* tile_frames;
+    int tile_cap;
+    void* links;
+    size_t links_cap;
+    int links_f4;
+    void* args;
+    size_t args_cap, args_bytes;
+} rt_debug_scene_out;
+int rt_debug_plan_scene(const rt_debug_scene_in* in, rt_debug_scene_out* out);
+
 /* The BVH the link walk of ctx uses, in the reference's node format (rt_bvh_node): the
  * uploaded one, or in RT_BVH_SAH mode the tree rt_set_bvh_mode builds (validated as by
  * rt_render).  out may be NULL to query *nbytes; returns RT_ERR_LIMIT if out_cap is short.

@@ -13,6 +13,7 @@
 #include "rt/rt.h"
 #include "rt/rt_debug.h"
 #include "rt/rt_types.h"
+#include "rt_args.h"
 #include "rt_device.h"
 #include "rt_prep.h"
 
@@ -71,133 +72,16 @@ struct Device {
 using rt_impl::Device;
 using rt_impl::FastTables;
 
-struct rt_ctx {
+// The scene, its options and frame counts are the base (rt_args.h: host-only, what rt_args.cpp works
+// on); the context adds the devices and the bookkeeping of what was launched, gathered and filtered.
+struct rt_ctx : rt_impl::SceneState {
     std::vector<Device> devs;
     std::string err;
-    // host copies of what the kernel needs
-    std::vector<uint8_t> host_buf[6];
-    bool uploaded[6] = {false, false, false, false, false, false};
-    int tex_format[8] = {0}, tex_w[8] = {0}, tex_h[8] = {0};
-    rt_camera_ubo cam{};
-    bool have_cam = false;
-    int max_depth = 5;
-    float background[3] = {0, 0, 0};
-    float sqrt_spp = 1.0f, recip_sqrt_spp = 1.0f;
-    int width = 0, height = 0;
-    int proc_rank = 0, proc_world = 1, stripe_rows = 16;
-    int n_dnodes = 0;
-    std::vector<rt_dnode> dnodes;   // host copy of the threaded BVH (fast-walk tables are built from it)
-    // the BVH the link walk runs on (rt_set_bvh_mode): the uploaded one (RT_BVH_REFERENCE), or the
-    // binned-SAH tree built from its prims at validation (RT_BVH_SAH, non-parity fast mode, bvh_sah.h)
-    int bvh_mode = RT_BVH_REFERENCE;
-    int n_link_nodes = 0;
-    std::vector<uint8_t> sah_bvh;   // the SAH tree in the reference's node format (rt_debug_walk_bvh)
-    std::vector<rt_dnode> walk_dn;  // threaded nodes of the BVH the link walk uses (reference or SAH)
-    // the links the launch walks: c->links, or (option box_vnodes) the same with every all-box leaf's
-    // box pre-tests as nodes of the walk (build_links with vbox); rebuilt when the margin changes
-    std::vector<float4> walk_links;
-    int n_walk_nodes = 0;
-    bool walk_v = false;
-    float walk_v_margin = -1.0f;
-    bool walk_stale = true;
-    std::vector<float4> boxc_host;  // the compact box records (host copy of Device::dboxc)
-    bool box_vnodes = true;         // option box_vnodes
-    bool box_interior = true;       // option box_interior
-    bool zero_dir_end = true;       // option zero_dir_end (rt_kernel.hip render_stream)
-    bool first_leaf = true;         // option first_leaf: a walk that starts at the spine's leaf tests it where
-                                    // it begins (rt_kernel.hip render_stream; the RT_OPT_BOXQ kernels)
-    int first_leaf_last[4] = {0};   // rt_debug_first_leaf: the last launch's (armed, leaf link, type byte, prims)
-    bool collapse = true;           // option collapse: the walk leaves out inner nodes (plan_collapse)
-    int rebuild = 2;                // option rebuild: the walk's inner nodes rebuilt over its leaves (rebuild_inner mode)
-    bool walk_r = false;            // walk_links were built on the rebuilt inner nodes
-    int walk_rmode = 0;             // ... of this mode
-    std::vector<rt_dnode> rb_dn;    // rebuild_inner(walk_dn, rb_mode), kept across camera moves
-    int rb_mode = -1;               // -1: not built for the current walk_dn
-    bool walk_c = false;            // walk_links were built with a collapse plan ...
-    rt_camera_ubo walk_cam{};       // ... for this camera and image size
-    int walk_w = 0, walk_h = 0;
-    int n_dropped = 0;              // inner nodes the walk leaves out
-    int n_rebuilt = 0;              // nodes of the rebuilt tree (0: the tree as uploaded / built)
-    int n_vnodes = 0;               // box pre-test nodes in walk_links
-    FastTables fast;
-    std::vector<float4> links;   // build_links(dnodes), empty when unavailable
-    int fast_gen = 0;
-    bool spec_ok = false;   // every child box lies inside its parent's (the near-first walk needs it)
-    int debug_flags = 0;    // env RT_DEBUG_FLAGS: ablation runs only (bit 0: Perlin -> 0.5; bit 3: compact boxes hit on their planes alone)
-    bool uv_always = false;
-    bool boxes_canon = false;   // every box has Box.java's axis-aligned face layout (dboxes[18..20])
-    bool fd_ok[6] = {true, true, true, true, true, true};   // per binding: records in the fast-division regime
-    bool fd_cam = true;
-    bool boxes_cond = false;   // every box face's 2-D Cramer system is well conditioned (box pre-test)
-    float scene_extent = -1.0f;   // max |coordinate| over records and camera (< 0: not computed)
-    bool validated = false;
     uint64_t last_ns = 0;
-    int variant = 0;   // kernel structure variant (env RT_KERNEL_VARIANT; A/B only)
     int variant_no_stats = -1;   // the variant active before rt_debug_enable_stats(c, 1), restored by (c, 0)
-    // the collapse plan from measured node hits (rt_debug_set_collapse_hits): per node of the walk's
-    // tree in its breadth-first link order, the box tests that hit, and the walks begun at the root
-    std::vector<int64_t> inj_hits;
-    int64_t inj_walks = 0;
-    // Work split: aim for chunk_target work units per resident wave (env
-    // RT_CHUNK_TARGET; 0 = one chunk per tile), staged_chunk_target when staged
-    // (RT_STAGED_CHUNK_TARGET).  With at least stage_tiles tiles
-    // per resident wave (env RT_STAGE_TILES) the chunks are ordered (the running
-    // mean is handed from wave to wave, rt_kernel.hip wait_chunk); with fewer, a
-    // tile's frames would be one long serial chain, so the chunks run in parallel,
-    // stage their per-frame colours (at most sample_budget bytes) and the fold (rt_moments.hip)
-    // applies the running mean in frame order.  The default stage_tiles stages
-    // every chunked launch: with render_stream that measured fastest at N = 1 too
-    // (scene 8 -5% against ordered chunks).
-    int chunk_target = 16;          // ordered chunks (RT_CHUNK_TARGET)
-    int staged_chunk_target = 48;   // staged chunks (RT_STAGED_CHUNK_TARGET)
-    int tail_chunks = -1;           // option tail_chunks: staged launches end with this many one-frame chunks
-                                    // (-1: tail_chunks_for the tree)
-    int stage_tiles = 1 << 20;      // in effect always staged (the measured best with render_stream)
-    bool fastdiv = true;   // shared-reciprocal divisions where exact (env RT_FASTDIV=0 disables; A/B)
-    bool box_pretest = true;   // the canonical box tests' bounds pre-test (env RT_BOX_PRETEST=0 disables; A/B)
-    int sm_batch = 64;   // render_stream's shading batch (env RT_SM_BATCH) ...
-    int sm_frac = 0;     // ... or fraction of the lanes with a walk, in 64ths (env RT_SM_FRAC); 0 = by kernel:
-                         // 50 for the compact-box kernels (scene 8 1080p -1.1%, 4K -1.6% against 56), 56 else
-                         // (scene 6 +1.4% at 52; profiles/r03_sm_frac_knobs.log)
-    bool shade_lds = true;       // shading tables in LDS (sphere / box materials, small textures; option):
-                                 // scenes 8 / 0 / 6 -0.3 / -1.0 / -1.2% (profiles/r04_shade_lds_ab_s*.log)
-    bool tl_small_lds = true;    // two-level walk: small sphere / box tables staged beside the top levels (option)
-    bool leaf_prefetch = true;   // leaf records prefetched before the type blocks when all are in LDS (option)
-    int walk_frac = 0;   // render_stream: node walks stop at this fraction of lanes ready, in 64ths (env RT_WALK_FRAC);
-                         // 0 = by BVH size: 8 up to 64 nodes, 32 up to 1024, 48 above (walk_frac_for)
-    bool big_wg = true;    // 1024-thread workgroups with sphere + box records in LDS when they fit (env RT_BIG_WG=0: A/B)
-    bool sph_lds = true;   // sphere records' first two float4 in LDS when they fit (env RT_SPH_LDS=0 disables; A/B)
-    bool compact_boxes = true;   // boxes' compact records when every box has one (box_test_compact; option 0: A/B)
-    bool spine = true;           // walks start past the spine when they hit it for sure (plan_spine)
-    int lds_node_cap = 0;        // bytes of BVH nodes staged in LDS, 0 = as many as fit (tests: force the two-level walk)
-    bool tl_leaf_lds = true;     // two-level walk: the leaf records in LDS beside the top levels (when they fit)
-    int perlin_pk_slot = -1;     // texture slot whose Perlin table has its packed copy (Device::perlin_pk)
-    bool sparse_stage = true;    // staged chunks store only the colours that are not exactly zero (option)
-    int sphere_pairs = 1;        // the sphere-pair kernels when most leaves hold two spheres (option; 2: always,
-                                 // compact-box kernels included)
-    int pair_leaves = -1;        // per mille of the link-format leaves that hold two spheres (< 0: not counted)
-    bool perlin_pk = true;       // stage the packed Perlin table (option; else the texture as uploaded)
-    int n_boxc_ok = 0;           // boxes whose compact record reproduces their faces
-    unsigned long long watchdog_ticks = 120ull * 100000000ull;     // render_stream progress bound (100 MHz ticks)
-    unsigned long long chunk_wait_ticks = 30ull * 100000000ull;    // ordered-chunk wait bound
-    size_t sample_budget = (size_t)32 << 30;   // staged colours per launch, at most (and at most half the free memory)
     int last_launch[RT_LI_N] = {0};
+    int first_leaf_last[4] = {0};   // rt_debug_first_leaf: the last launch's (armed, leaf link, type byte, prims)
     bool launched = false;
-    // Sample moments (rt_set_moments; single-device contexts): every launch is staged and folded by
-    // the fold with the moments.  moments_frames = the frames 1 .. n whose moments Device::m2 holds, 0 =
-    // invalid (nothing rendered yet, a first_frame gap, the image overwritten or resized).
-    bool moments = false;
-    int moments_frames = 0;
-    // Per-tile frame counts (rt_read_tile_frames): the frames 1 .. n each 8x8 tile of the first device's
-    // image holds, 0 = invalid.  While every tile holds the same count tile_frames is empty and
-    // moments_frames is that count; once they differ (a launch under a tile mask) tile_frames holds
-    // one count per tile and moments_frames their minimum, so "valid" stays moments_frames >= 1.
-    // Single-device contexts keep them whether or not the moments are on.
-    std::vector<int32_t> tile_frames;
-    // rt_set_active_tiles: the mask in effect (mask_set), its tiles' indices in ascending order
-    // (Device::tile_list holds the same on the device)
-    bool mask_set = false;
-    std::vector<int32_t> act_list;
     // rt_denoise: which of Device::dn_px holds the filtered image (-1: none held), and the per-tile
     // counts last copied to Device::dn_counts (copied again only when they change)
     int dn_result = -1;
@@ -308,8 +192,8 @@ inline int ensure(rt_ctx* c, Device& d, DevBuf& b, size_t n) {
     return RT_OK;
 }
 
-// rt_capi.hip: checks the uploaded records against each other and derives the walk's trees
-int validate(rt_ctx* c);
+// validate(SceneState&) of rt_args.h with its error text in the context
+inline int validate(rt_ctx* c) { return validate(*c, &c->err); }
 // rt_comm.hip (the RCCL table and its state stay in that unit)
 int device_gather(rt_ctx* c);
 void comm_destroy(Device& d);   // rt_destroy: frees the device's communicator, if any

@@ -195,90 +195,20 @@ int rt_debug_ab_build(void) {
 #endif
 }
 
+#ifdef RT_AB_KNOBS
+static const bool kAbOptions = true;
+#else
+static const bool kAbOptions = false;
+#endif
+
 int rt_debug_set_option(rt_ctx* c, int option, int v) {
     if (!c) return RT_ERR_INVALID_ARG;
-    auto bad = [&]() { return set_err(c, RT_ERR_INVALID_ARG, "option value out of range"); };
-    switch (option) {
-        case RT_OPTION_BOX_PRETEST: c->box_pretest = v != 0; break;
-        case RT_OPTION_FASTDIV: c->fastdiv = v != 0; break;
-        case RT_OPTION_SPH_LDS: c->sph_lds = v != 0; break;
-        case RT_OPTION_BIG_WG: c->big_wg = v != 0; break;
-        case RT_OPTION_COMPACT_BOXES: c->compact_boxes = v != 0; break;
-        case RT_OPTION_SPINE: c->spine = v != 0; break;
-        case RT_OPTION_TL_LEAF_LDS: c->tl_leaf_lds = v != 0; break;
-        case RT_OPTION_PERLIN_PACKED: c->perlin_pk = v != 0; break;
-        case RT_OPTION_SPARSE_STAGE: c->sparse_stage = v != 0; break;
-        case RT_OPTION_SPHERE_PAIRS: if (v < 0 || v > 2) return bad(); c->sphere_pairs = v; break;
-        case RT_OPTION_LEAF_PREFETCH: c->leaf_prefetch = v != 0; break;
-        case RT_OPTION_TL_SMALL_LDS: c->tl_small_lds = v != 0; break;
-        case RT_OPTION_SHADE_LDS: c->shade_lds = v != 0; break;
-        case RT_OPTION_BOX_VNODES: c->box_vnodes = v != 0; break;
-        case RT_OPTION_BOX_INTERIOR: c->box_interior = v != 0; break;
-        case RT_OPTION_ZERO_DIR_END: c->zero_dir_end = v != 0; break;
-        case RT_OPTION_FIRST_LEAF: c->first_leaf = v != 0; break;
-        case RT_OPTION_COLLAPSE: c->collapse = v != 0; break;
-        case RT_OPTION_REBUILD: if (v < 0 || v > 2) return bad(); c->rebuild = v; break;
-        case RT_OPTION_CHUNK_TARGET: if (v < 0) return bad(); c->chunk_target = v; break;
-        case RT_OPTION_STAGED_CHUNK_TARGET: if (v < 1) return bad(); c->staged_chunk_target = v; break;
-        case RT_OPTION_STAGE_TILES: if (v < 0) return bad(); c->stage_tiles = v; break;
-        case RT_OPTION_SM_BATCH: if (v < 1 || v > 64) return bad(); c->sm_batch = v; break;
-        case RT_OPTION_SM_FRAC: if (v < 0 || v > 64) return bad(); c->sm_frac = v; break;
-        case RT_OPTION_WALK_FRAC: if (v < 0 || v > 64) return bad(); c->walk_frac = v; break;
-        case RT_OPTION_WATCHDOG_MS: if (v < 0) return bad(); c->watchdog_ticks = (unsigned long long)v * 100000ull; break;
-        case RT_OPTION_CHUNK_WAIT_MS: if (v < 0) return bad(); c->chunk_wait_ticks = (unsigned long long)v * 100000ull; break;
-        case RT_OPTION_LDS_NODE_CAP: if (v < 0) return bad(); c->lds_node_cap = v; break;
-        case RT_OPTION_TAIL_CHUNKS: if (v < -1 || v > RT_MAX_FRAMES_PER_LAUNCH) return bad(); c->tail_chunks = v; break;
-#ifdef RT_AB_KNOBS
-        case RT_OPTION_KERNEL_VARIANT:
-            if (!(v == 0 || v == 30 || v == 31 || v == 37 || v == 38 || v == 39 || v == 61 || v == 69)) return bad();
-            c->variant = v;
-            break;
-        case RT_OPTION_DEBUG_FLAGS: c->debug_flags = v; break;
-#endif
-        default: return set_err(c, RT_ERR_INVALID_ARG, "unknown option (A/B options need librtamd_ab.so)");
-    }
-    return RT_OK;
+    return set_option(*c, option, v, kAbOptions, &c->err);
 }
 
 int rt_debug_get_option(rt_ctx* c, int option, int* v) {
     if (!c || !v) return RT_ERR_INVALID_ARG;
-    switch (option) {
-        case RT_OPTION_BOX_PRETEST: *v = c->box_pretest; break;
-        case RT_OPTION_FASTDIV: *v = c->fastdiv; break;
-        case RT_OPTION_SPH_LDS: *v = c->sph_lds; break;
-        case RT_OPTION_BIG_WG: *v = c->big_wg; break;
-        case RT_OPTION_COMPACT_BOXES: *v = c->compact_boxes; break;
-        case RT_OPTION_SPINE: *v = c->spine; break;
-        case RT_OPTION_TL_LEAF_LDS: *v = c->tl_leaf_lds; break;
-        case RT_OPTION_PERLIN_PACKED: *v = c->perlin_pk; break;
-        case RT_OPTION_SPARSE_STAGE: *v = c->sparse_stage; break;
-        case RT_OPTION_SPHERE_PAIRS: *v = c->sphere_pairs; break;
-        case RT_OPTION_LEAF_PREFETCH: *v = c->leaf_prefetch; break;
-        case RT_OPTION_TL_SMALL_LDS: *v = c->tl_small_lds; break;
-        case RT_OPTION_SHADE_LDS: *v = c->shade_lds; break;
-        case RT_OPTION_BOX_VNODES: *v = c->box_vnodes; break;
-        case RT_OPTION_BOX_INTERIOR: *v = c->box_interior; break;
-        case RT_OPTION_ZERO_DIR_END: *v = c->zero_dir_end; break;
-        case RT_OPTION_FIRST_LEAF: *v = c->first_leaf; break;
-        case RT_OPTION_COLLAPSE: *v = c->collapse; break;
-        case RT_OPTION_REBUILD: *v = c->rebuild; break;
-        case RT_OPTION_CHUNK_TARGET: *v = c->chunk_target; break;
-        case RT_OPTION_STAGED_CHUNK_TARGET: *v = c->staged_chunk_target; break;
-        case RT_OPTION_STAGE_TILES: *v = c->stage_tiles; break;
-        case RT_OPTION_SM_BATCH: *v = c->sm_batch; break;
-        case RT_OPTION_SM_FRAC: *v = c->sm_frac; break;
-        case RT_OPTION_WALK_FRAC: *v = c->walk_frac; break;
-        case RT_OPTION_WATCHDOG_MS: *v = (int)std::min<unsigned long long>(INT_MAX, c->watchdog_ticks / 100000ull); break;
-        case RT_OPTION_CHUNK_WAIT_MS: *v = (int)std::min<unsigned long long>(INT_MAX, c->chunk_wait_ticks / 100000ull); break;
-        case RT_OPTION_LDS_NODE_CAP: *v = c->lds_node_cap; break;
-        case RT_OPTION_TAIL_CHUNKS: *v = c->tail_chunks; break;
-#ifdef RT_AB_KNOBS
-        case RT_OPTION_KERNEL_VARIANT: *v = c->variant; break;
-        case RT_OPTION_DEBUG_FLAGS: *v = c->debug_flags; break;
-#endif
-        default: return set_err(c, RT_ERR_INVALID_ARG, "unknown option (A/B options need librtamd_ab.so)");
-    }
-    return RT_OK;
+    return get_option(*c, option, v, kAbOptions, &c->err);
 }
 
 int rt_debug_walk_bvh(rt_ctx* c, void* out, size_t out_cap, size_t* nbytes) {

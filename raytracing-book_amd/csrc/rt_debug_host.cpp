@@ -1,6 +1,6 @@
 // rt_debug_host.cpp — the C ABI's entries that need no context and no device: the stripe
 // arithmetic and frame factors of rt.h, and rt_debug.h's views of the host-only scene
-// preparation (rt_prep.h).  Plain C++, built once and linked into both libraries; with
+// preparation (rt_prep.h), launch planning (rt_plan.h) and argument assembly (rt_args.h).  Plain C++, built once and linked into both libraries; with
 // rt_prep.cpp it links into a stand-alone program (tools/fuzz).
 #include <algorithm>
 #include <cmath>
@@ -10,6 +10,7 @@
 #include "rt/rt.h"
 #include "rt/rt_debug.h"
 #include "rt/rt_types.h"
+#include "rt_args.h"
 #include "rt_plan.h"
 #include "rt_prep.h"
 #include "bvh_sah.h"
@@ -284,6 +285,153 @@ int rt_debug_plan_kernel(const int* in, int n_in, int ab, int* out, int n_out, i
     out[RT_PKO_OPT] = k.opt;
     out[RT_PKO_LDS_BYTES] = (int)k.lds;
     std::memcpy(info, k.info, sizeof(int) * RT_LI_N);
+    return RT_OK;
+}
+
+// rt_debug_plan_kernel's RT_PK_* view of a launch's arguments (the inverse of its reading above)
+static void pk_from_args(const rt_kernel_args& a, int* pk) {
+    pk[RT_PK_VARIANT] = a.variant;
+    pk[RT_PK_BLOCK] = a.block;
+    pk[RT_PK_N_ACTIVE] = a.n_active;
+    pk[RT_PK_SAMPLES] = a.samples != nullptr;
+    pk[RT_PK_SFLAGS] = a.sflags != nullptr;
+    pk[RT_PK_WBUF] = a.wbuf != nullptr;
+    pk[RT_PK_TILE_LIST] = a.tile_list != nullptr;
+    pk[RT_PK_N_NODES] = a.n_nodes;
+    pk[RT_PK_N_LNODE_F4] = a.n_lnode_f4;
+    pk[RT_PK_LDS_NODE_F4] = a.lds_node_f4;
+    pk[RT_PK_LDS_END_F4] = a.lds_end_f4;
+    pk[RT_PK_N_F2INNER] = a.n_f2inner;
+    pk[RT_PK_N_F2LEAVES] = a.n_f2leaves;
+    pk[RT_PK_FASTDIV] = a.fastdiv;
+    pk[RT_PK_BOX_ALL_CMP] = a.box_all_cmp;
+    pk[RT_PK_BOX_INTERIOR] = a.box_interior;
+    pk[RT_PK_SPH_PAIRS] = a.sph_pairs;
+    pk[RT_PK_LEAF_PF] = a.leaf_pf;
+    pk[RT_PK_MEDIA_SPH] = a.media_sph;
+    pk[RT_PK_N_MEDIA] = a.n_media;
+    pk[RT_PK_N_SPH_LDS] = a.n_sph_lds;
+    pk[RT_PK_N_BOX_LDS] = a.n_box_lds;
+    pk[RT_PK_PERLIN_LDS] = a.perlin_lds;
+    pk[RT_PK_MEDIA_LDS] = a.media_lds;
+    pk[RT_PK_SPH_LDS] = a.sph_lds;
+    pk[RT_PK_BOX_CMP_LDS] = a.box_cmp_lds;
+    pk[RT_PK_SPH_MAT_LDS] = a.sph_mat_lds;
+    pk[RT_PK_BOX_MAT_LDS] = a.box_mat_lds;
+    pk[RT_PK_TEX_LDS] = a.tex_lds;
+    pk[RT_PK_PRETEST] = a.box_margin > 0.0f;
+    pk[RT_PK_N_CHUNKS] = a.n_chunks;
+    pk[RT_PK_SPINE_LEN] = a.spine_len;
+    pk[RT_PK_WALK_FRAC] = a.walk_frac;
+}
+
+int rt_debug_plan_scene(const rt_debug_scene_in* in, rt_debug_scene_out* out) {
+    if (!in || !out || !in->camera || in->first_frame < 1 || in->n_frames < 0 || in->waves < 0 || in->n_options < 0 ||
+        (in->n_options && !in->options) || (in->n_mask > 0 && !in->mask))
+        return RT_ERR_INVALID_ARG;
+    // rt_resize's and rt_set_partition's argument checks
+    if (in->width <= 0 || in->height <= 0 || in->width > RT_MAX_IMAGE_DIM || in->height > RT_MAX_IMAGE_DIM ||
+        (size_t)in->width * in->height > ((size_t)1 << 30) || in->world < 1 || in->rank < 0 || in->rank >= in->world ||
+        in->stripe_rows < 1 || in->max_depth < 0 || (in->bvh_mode != RT_BVH_REFERENCE && in->bvh_mode != RT_BVH_SAH))
+        return RT_ERR_INVALID_ARG;
+    static float4 there[1];   // stands for a buffer the device part of rt_render would hold
+    int* const tile_frames = out->tile_frames;
+    const int tile_cap = out->tile_cap;
+    void* const links = out->links;
+    void* const args = out->args;
+    const size_t links_cap = out->links_cap, args_cap = out->args_cap;
+    std::memset(out, 0, sizeof(*out));
+    out->tile_frames = tile_frames; out->tile_cap = tile_cap;
+    out->links = links; out->links_cap = links_cap;
+    out->args = args; out->args_cap = args_cap;
+    SceneState s;
+    int r;
+    for (int k = 0; k < in->n_options; k++)
+        if ((r = set_option(s, in->options[2 * k], in->options[2 * k + 1], in->ab != 0, nullptr))) return r;
+    s.bvh_mode = in->bvh_mode;
+    for (int b = 0; b < 6; b++) {
+        BufferPrep p;
+        if ((r = prep_buffer(s, b, in->buf[b], in->buf_bytes[b], p, nullptr))) return r;
+    }
+    for (int t = 0; t < RT_MAX_TEXTURES; t++) {
+        if (in->tex_w[t] == 0) continue;
+        TexturePrep p;
+        if ((r = prep_texture(t, in->tex_format[t], in->tex_w[t], in->tex_h[t], in->tex[t], p, nullptr))) return r;
+        set_texture(s, t, in->tex_format[t], in->tex_w[t], in->tex_h[t], !p.pk.empty());
+    }
+    set_camera(s, in->camera);
+    s.max_depth = in->max_depth;
+    std::memcpy(s.background, in->background, 12);
+    s.sqrt_spp = in->sqrt_spp;
+    s.recip_sqrt_spp = in->recip_sqrt_spp;
+    s.width = in->width; s.height = in->height;
+    s.proc_rank = in->rank; s.proc_world = in->world; s.stripe_rows = in->stripe_rows;
+    s.moments = in->moments != 0;
+    const int local_rows = local_rows_of(s.height, in->rank, in->world, s.stripe_rows);
+    const int nt = tile_count(s.width, local_rows);
+    if (in->n_mask >= 0) {
+        for (int k = 0; k < in->n_mask; k++)
+            if (in->mask[k] < 0 || in->mask[k] >= nt || (k && in->mask[k] <= in->mask[k - 1])) return RT_ERR_INVALID_ARG;
+        s.mask_set = true;
+        s.act_list.assign(in->mask, in->mask + in->n_mask);
+    }
+    s.moments_frames = in->prev_frames;
+    if (in->prev_tile_frames) s.tile_frames.assign(in->prev_tile_frames, in->prev_tile_frames + nt);
+    // rt_render from here
+    if ((r = validate(s, nullptr))) return r;
+    rt_kernel_args a;
+    if ((r = scene_args(s, a, nullptr))) return r;
+    const bool mom = s.moments && in->n_frames > 0 && local_rows > 0;
+    if (s.mask_set && !pooled_variant(s.variant)) return RT_ERR_STATE;
+    FrameCounts after;
+    after.all = s.moments_frames;
+    after.tiles = s.tile_frames;
+    if (in->n_frames > 0 && local_rows > 0)
+        after = step_frame_counts(s.moments_frames, s.tile_frames, nt, s.mask_set ? &s.act_list : nullptr, in->first_frame,
+                                  in->n_frames);
+    out->frames_all = after.all;
+    out->n_tile_frames = (int)after.tiles.size();
+    if (!after.tiles.empty()) {
+        if (!tile_frames || tile_cap < (int)after.tiles.size()) return RT_ERR_LIMIT;
+        std::memcpy(tile_frames, after.tiles.data(), after.tiles.size() * sizeof(int32_t));
+    }
+    out->links_f4 = (int)s.walk_links.size();
+    if (links) {
+        if (links_cap < s.walk_links.size() * sizeof(float4)) return RT_ERR_LIMIT;
+        if (!s.walk_links.empty()) std::memcpy(links, s.walk_links.data(), s.walk_links.size() * sizeof(float4));
+    }
+    out->args_bytes = sizeof(rt_kernel_args);
+    if (args && args_cap < sizeof(rt_kernel_args)) return RT_ERR_LIMIT;
+    int info[RT_LI_N] = {0};
+    if (!(s.mask_set && s.act_list.empty()) && in->n_frames > 0 && local_rows > 0) {
+        // the device's part of rt_render (render_device) as numbers: bind_device's stripe, then the plans
+        a.local_rows = local_rows;
+        a.rank = in->rank;
+        a.world = in->world;
+        const Split split = plan_device(s, local_rows, in->waves, in->free_bytes, mom, in->n_frames, a);
+        a.tile_list = s.mask_set ? (const int*)there : nullptr;
+        const LaunchPlan p = plan_launch(s, split, mom, in->waves, in->first_frame, in->n_frames, 0, a);
+        a.samples = p.stage ? there : nullptr;
+        a.sflags = p.sparse ? (uint8_t*)there : nullptr;
+        a.wbuf = p.wave_slots ? there : nullptr;
+        out->launched = 1;
+        pk_from_args(a, out->pk);
+        out->per_launch = split.per_launch; out->chunks_wanted = split.chunks_wanted; out->staged = split.staged;
+        out->n_chunks = a.n_chunks; out->chunk_frames = a.chunk_frames; out->tail_chunks = a.tail_chunks;
+        out->stage = p.stage;
+        rt_kernel_args planned = a;   // (plan_kernel edits its copy: args stays what rt_render assembled)
+        const KernelPlan k = plan_kernel(planned, in->ab != 0);
+        if (k.ok) std::memcpy(info, k.info, sizeof(info));
+        launch_report(s, a, info, out->first_leaf);
+        out->bvh_mode = info[RT_LI_BVH_MODE]; out->vnodes = info[RT_LI_VNODES];
+        out->collapsed = info[RT_LI_COLLAPSED]; out->rebuilt = info[RT_LI_REBUILT];
+        std::memcpy(out->first_leaf_args, a.first_leaf, sizeof(out->first_leaf_args));
+        out->spine_start = a.spine_start;
+        a.samples = nullptr; a.sflags = nullptr; a.wbuf = nullptr; a.tile_list = nullptr;
+        if (args) std::memcpy(args, &a, sizeof(a));
+    } else if (args) {
+        std::memset(args, 0, sizeof(rt_kernel_args));
+    }
     return RT_OK;
 }
 

@@ -16,7 +16,7 @@ namespace rt_impl __attribute__((visibility("hidden"))) {
 // the lanes' running means after what is staged) and 61 (its own tree) plan below too.
 void plan_lds(const LdsIn& in, rt_kernel_args& a) {
     const bool fast_walk = in.variant == 61 || in.variant == 69;
-    const bool pooled = in.variant == 0 || in.variant == 39;
+    const bool pooled = pooled_variant(in.variant);
     const int n_sph = in.n_sph, n_box = in.n_box, n_med = in.n_med;
     const size_t node_f4 = 2 * (size_t)in.n_walk_nodes;
     const size_t leaf_f4 = (size_t)in.n_lnode_f4 > node_f4 ? (size_t)in.n_lnode_f4 - node_f4 : 0;
@@ -154,7 +154,7 @@ KernelPlan plan_kernel(rt_kernel_args& a, bool ab) {
     if (tl) shape = RT_SHAPE_LINK_TL;
     if (ab) {
         stats = a.variant == 38 || a.variant == 31 || a.variant == 69 || a.variant == 39;
-        pool = a.variant == 0 || a.variant == 39;
+        pool = pooled_variant(a.variant);
         if (a.variant == 61 || a.variant == 69) {
             const size_t stack_b = (size_t)RT_FAST_STACK * 512 * sizeof(short);
             const size_t tree_b = (size_t)a.n_f2inner * 64 + (size_t)((a.n_f2leaves + 1) / 2) * 16;

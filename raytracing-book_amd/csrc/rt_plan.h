@@ -62,6 +62,12 @@
 
 namespace rt_impl __attribute__((visibility("hidden"))) {
 
+// the pooled kernel structure (the default and its stats twin): the only one the SAH tree, tile masks,
+// the collapse, rebuild and box pre-test nodes, sparse staging and the per-wave slots run on
+inline bool pooled_variant(int variant) { return variant == 0 || variant == 39; }
+// 8x8 tiles of `rows` rows of an image
+inline int tile_count(int width, int rows) { return ((width + 7) / 8) * ((rows + 7) / 8); }
+
 struct KernelId {
     int block, opt;
 };

@@ -84,6 +84,35 @@ class RtDenoiseParams(ctypes.Structure):
     _fields_ = [("levels", ctypes.c_int), ("k", ctypes.c_float), ("reserved", ctypes.c_int * 6)]
 
 
+RT_PK_N = 33   # rt_debug.h RT_PK_N
+
+
+class RtDebugSceneIn(ctypes.Structure):
+    """rt_debug.h rt_debug_scene_in."""
+    _fields_ = [("buf", ctypes.c_void_p * 6), ("buf_bytes", ctypes.c_size_t * 6),
+                ("tex_format", ctypes.c_int * 8), ("tex_w", ctypes.c_int * 8), ("tex_h", ctypes.c_int * 8),
+                ("tex", ctypes.c_void_p * 8), ("camera", c_float_p), ("max_depth", ctypes.c_int),
+                ("background", ctypes.c_float * 3), ("sqrt_spp", ctypes.c_float), ("recip_sqrt_spp", ctypes.c_float),
+                ("width", ctypes.c_int), ("height", ctypes.c_int), ("rank", ctypes.c_int), ("world", ctypes.c_int),
+                ("stripe_rows", ctypes.c_int), ("options", c_int_p), ("n_options", ctypes.c_int), ("ab", ctypes.c_int),
+                ("bvh_mode", ctypes.c_int), ("moments", ctypes.c_int), ("mask", c_int_p), ("n_mask", ctypes.c_int),
+                ("prev_frames", ctypes.c_int), ("prev_tile_frames", c_int_p), ("first_frame", ctypes.c_int),
+                ("n_frames", ctypes.c_int), ("waves", ctypes.c_longlong), ("free_bytes", ctypes.c_size_t)]
+
+
+class RtDebugSceneOut(ctypes.Structure):
+    """rt_debug.h rt_debug_scene_out."""
+    _fields_ = [("pk", ctypes.c_int * RT_PK_N), ("launched", ctypes.c_int), ("bvh_mode", ctypes.c_int),
+                ("vnodes", ctypes.c_int), ("collapsed", ctypes.c_int), ("rebuilt", ctypes.c_int),
+                ("first_leaf", ctypes.c_int * 4), ("first_leaf_args", ctypes.c_uint * 3), ("spine_start", ctypes.c_uint),
+                ("per_launch", ctypes.c_int), ("chunks_wanted", ctypes.c_int), ("staged", ctypes.c_int),
+                ("n_chunks", ctypes.c_int), ("chunk_frames", ctypes.c_int), ("tail_chunks", ctypes.c_int),
+                ("stage", ctypes.c_int), ("frames_all", ctypes.c_int), ("n_tile_frames", ctypes.c_int),
+                ("tile_frames", c_int_p), ("tile_cap", ctypes.c_int), ("links", ctypes.c_void_p),
+                ("links_cap", ctypes.c_size_t), ("links_f4", ctypes.c_int), ("args", ctypes.c_void_p),
+                ("args_cap", ctypes.c_size_t), ("args_bytes", ctypes.c_size_t)]
+
+
 def _amd_protos(L, old_rev=False):
     vp, sz, i, f, u64 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_float, ctypes.c_uint64
     ts_p, ns_p = ctypes.POINTER(RtTileSum), ctypes.POINTER(RtNoiseStats)
@@ -164,6 +193,8 @@ def _amd_protos(L, old_rev=False):
     _proto(L, "rt_debug_last_launch", i, vp, c_int_p, i)
     if not old_rev or hasattr(L, "rt_debug_plan_kernel"):   # ... or from before the host-side launch plan
         _proto(L, "rt_debug_plan_kernel", i, c_int_p, i, i, c_int_p, i, c_int_p, c_int_p, i, c_int_p)
+    if not old_rev or hasattr(L, "rt_debug_plan_scene"):   # ... or from before the host-side argument assembly
+        _proto(L, "rt_debug_plan_scene", i, ctypes.POINTER(RtDebugSceneIn), ctypes.POINTER(RtDebugSceneOut))
     if not old_rev or hasattr(L, "rt_debug_first_leaf"):   # ... or from before the first-leaf prologue
         _proto(L, "rt_debug_first_leaf", i, vp, c_int_p)
     _proto(L, "rt_set_bvh_mode", i, vp, i)

@@ -65,6 +65,81 @@ def sah_bvh(scene, order=2, eye=None, prim_cost=1.0, lib=None):
     return out.raw[:n.value]
 
 
+def plan_scene(scene, frames, first_frame=1, width=None, height=None, options=None, ab=False, bvh_mode=0,
+               moments=False, mask=None, prev_frames=0, prev_tile_frames=None, rank=0, world=1, stripe_rows=16,
+               max_depth=5, spp=None, waves=4096, free_bytes=1 << 38, want_links=False, want_args=False, lib=None):
+    """rt_debug_plan_scene (no device needed): what rt_render would assemble and launch first for a Scene,
+    as a dict -- "pk" (int32 array: rt_debug_plan_kernel's input), "launched", the scene's last_launch
+    fields ("bvh_mode", "box_vnodes", "collapsed", "rebuilt"), "first_leaf" (rt_debug_first_leaf's four
+    words), the split and chunks, "tile_frames" (the counts after the call, one per tile of the stripe),
+    and on request "links" (float32 array) and "args" (the argument block's bytes).  mask: ascending tile
+    indices; options: dict name -> int as for RenderContext."""
+    L = lib or _lib.amd()
+    i = _lib.RtDebugSceneIn()
+    keep = []
+    for k in range(6):
+        data = scene.buffers[k]
+        b = ctypes.create_string_buffer(data, len(data)) if data else None
+        keep.append(b)
+        i.buf[k] = ctypes.addressof(b) if b is not None else None
+        i.buf_bytes[k] = len(data)
+    for t in scene.textures:
+        b = ctypes.create_string_buffer(t.data, len(t.data))
+        keep.append(b)
+        i.tex[t.slot] = ctypes.addressof(b)
+        i.tex_format[t.slot], i.tex_w[t.slot], i.tex_h[t.slot] = t.format, t.width, t.height
+    cam = np.ascontiguousarray(scene.camera, dtype=np.float32)
+    i.camera = cam.ctypes.data_as(c_float_p)
+    i.max_depth = int(max_depth)
+    i.background[:] = [float(x) for x in scene.background]
+    i.sqrt_spp, i.recip_sqrt_spp = spp_uniforms(spp or frames)
+    i.width, i.height = int(width or scene.width), int(height or scene.height)
+    i.rank, i.world, i.stripe_rows = int(rank), int(world), int(stripe_rows)
+    pairs = np.array([[OPTIONS[k], int(v)] for k, v in (options or {}).items()], np.int32).reshape(-1, 2)
+    i.options, i.n_options = pairs.ctypes.data_as(_lib.c_int_p), len(pairs)
+    i.ab, i.moments = int(bool(ab)), int(bool(moments))
+    i.bvh_mode = BVH_MODES[bvh_mode] if isinstance(bvh_mode, str) else int(bvh_mode)
+    m = None if mask is None else np.ascontiguousarray(mask, np.int32)
+    i.mask, i.n_mask = (None, -1) if m is None else (m.ctypes.data_as(_lib.c_int_p), int(m.size))
+    nt = ((i.width + 7) // 8) * ((local_rows(i.height, i.rank, i.world, i.stripe_rows) + 7) // 8)
+    i.prev_frames = int(prev_frames)
+    prev = None
+    if prev_tile_frames is not None:
+        prev = np.ascontiguousarray(prev_tile_frames, np.int32)
+        if prev.size != nt:
+            raise ValueError("one previous count per tile")
+        i.prev_tile_frames = prev.ctypes.data_as(_lib.c_int_p)
+    i.first_frame, i.n_frames = int(first_frame), int(frames)
+    i.waves, i.free_bytes = int(waves), int(free_bytes)
+    o = _lib.RtDebugSceneOut()
+    tiles = np.zeros(max(nt, 1), np.int32)
+    o.tile_frames, o.tile_cap = tiles.ctypes.data_as(_lib.c_int_p), nt
+    rc = L.rt_debug_plan_scene(ctypes.byref(i), ctypes.byref(o))
+    links = args = None
+    if rc == 0 and (want_links or want_args):   # the sizes are known now
+        links = np.zeros(4 * o.links_f4, np.float32)
+        args = np.zeros(o.args_bytes, np.uint8)
+        if want_links:
+            o.links, o.links_cap = links.ctypes.data, links.nbytes
+        if want_args:
+            o.args, o.args_cap = args.ctypes.data, args.nbytes
+        rc = L.rt_debug_plan_scene(ctypes.byref(i), ctypes.byref(o))
+    if rc != 0:
+        raise RTError(rc, "rt_debug_plan_scene failed")
+    out = {k: getattr(o, k) for k in ("launched", "bvh_mode", "collapsed", "rebuilt", "spine_start", "per_launch",
+                                     "chunks_wanted", "staged", "n_chunks", "chunk_frames", "tail_chunks", "stage")}
+    out["box_vnodes"] = o.vnodes
+    out["pk"] = np.array(o.pk[:], np.int32)
+    out["first_leaf"] = list(o.first_leaf)
+    out["first_leaf_args"] = list(o.first_leaf_args)
+    out["tile_frames"] = tiles[:nt].copy() if o.n_tile_frames else np.full(nt, o.frames_all, np.int32)
+    if want_links:
+        out["links"] = links
+    if want_args:
+        out["args"] = args
+    return out
+
+
 def local_rows(height, rank, world, stripe_rows):
     n_stripes = (height + stripe_rows - 1) // stripe_rows
     return sum(min(stripe_rows, height - s * stripe_rows) for s in range(rank, n_stripes, world))

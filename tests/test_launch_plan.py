@@ -11,6 +11,7 @@ computed on this code alone, it must choose nothing outside the table of instant
 entry of the table unused.
 """
 import ctypes
+import json
 import os
 import re
 
@@ -141,10 +142,29 @@ def test_reports_that_follow_the_chosen_kernel(golden):
 
 
 def test_golden_scenes_report_the_recorded_launches():
-    pytest.skip("plan_lds's inputs for a scene (the walk's node count after rebuild, collapse and box pre-test "
-                "nodes, the texture sizes, the packed Perlin table) are assembled inside rt_render from the "
-                "context and its device; no context-free entry gives them, so profiles/capi_split_lib_ab.log's "
-                "last_launch lines are checked by the GPU suite (tests/test_gpu_*.py pin rt_debug_last_launch)")
+    """Scenes 0-9 as tools/lib_ab.py renders them (1920x1080, 64 frames, spp 4096), through rt_debug_plan_scene
+    and then rt_debug_plan_kernel: every scene is planned, and the scenes profiles/pass_blocks_lib_ab_1.log
+    holds (8, 0, 6: what that call rendered) report every rt_debug_last_launch field the release library logged
+    on the MI355X (256 CUs: 4096 resident waves).  No field is left out: the free memory, the one input that
+    needs the device, changes only the frames per launch, which the report does not carry."""
+    logged = {}
+    for ln in open(os.path.join(PROFILES, "pass_blocks_lib_ab_1.log")):
+        m = re.match(r"scene (\d+) raytracing-book_amd/lib/librtamd\.so: last_launch (\{.*\})", ln)
+        if m:
+            logged[int(m.group(1))] = json.loads(m.group(2))
+    assert set(logged) == {8, 0, 6}
+    for sid in range(10):
+        sc = rtamd.Scene(sid, 1920, 1080, seed=1)
+        got = rtamd.plan_scene(sc, 64, spp=4096, waves=256 * 16)
+        assert got["launched"] == 1
+        out, info = plan(got["pk"][None, :], [0])
+        assert out[0][PKO["OK"]] == 1, sid
+        report = {n: int(info[0][k]) for n, k in LI.items()}
+        report.update({f: got[f] for f in ("bvh_mode", "box_vnodes", "collapsed", "rebuilt")})
+        report["shape_name"] = rtamd.render.SHAPES[report["shape"]]
+        assert report["tiles_active"] == 135 * 240 and report["staged"] == 1, sid
+        if sid in logged:
+            assert report == logged[sid], (sid, report, logged[sid])
 
 
 def test_argument_errors():
