@@ -15,6 +15,50 @@ extern "C" {
  * 3 acos, 4 atan2(x, y), 5 fract, 6 sqrt). */
 int rt_debug_eval_builtin(int device, int fn, const float* x, const float* y, float* out, int n);
 
+/* Evaluate one of the render kernels' own operations on `device`, one lane per row, by the device
+ * function the kernels call (csrc/rt_ops_eval.hip; tests/test_gpu_ops.py compares every form with
+ * the CPU oracle bit for bit).  Rows run in whole waves in input order (a batch that is no
+ * multiple of 64 is padded with copies of its last row), so the wave-wide ballots that choose a
+ * division form see the 64 rows the caller put together.
+ * Row i of `rows`: RT_OPS_ROW_F floats -- o[3], d[3], tmin, tmax, time, one int word, 2 unused.
+ * Row i of `out`: RT_OPS_OUT_W 32-bit words (floats as their bits; unused words 0).
+ * `recs`: one record per row as the scene uploads carry it; the host half prepares the device
+ * records with the functions the uploads run.
+ *   op                    recs per row            form                                   out words
+ *   RT_OP_SPHERE          rt_sphere (48 B)        0 '/', 1 shared reciprocal (sphere_t_ab), hit, t
+ *                                                 2 / 3 the same through sphere_t
+ *   RT_OP_MEDIUM_SPHERE   rt_sphere               0 '/', 1 shared reciprocal (sphere_bounds)  ok, t1, t2
+ *   RT_OP_QUAD            rt_quad (80 B)          0 '/', 1 shared reciprocal (quad_test)  hit, t, alpha, beta
+ *   RT_OP_BOX             6 rt_quad (480 B)       0 / 1 box_test plain / fd, 2 / 3         hit, t, face, alpha, beta
+ *                                                 box_test_compact plain / fd, 4 box_test_compact_q
+ *   RT_OP_NODE            6 floats (xmin, xmax,   0 aabb_fast, 1 aabb_pk, 2 the exact     hit
+ *                         ymin, ymax, zmin, zmax) per-axis slab (inv = 1 / d)
+ *   RT_OP_PERLIN          none; tex = the 6 x 256 0 perlin_turb_global, 1 perlin_turb_lds  |turbulence| at p = o
+ *                         R32F table              (the packed table staged in LDS)
+ *   RT_OP_SPHERE_UV       none                    0 (sphere_uv)                            u, v at p = o
+ *   RT_OP_TEXTURE         none; tex = slot 0's    0 (texture_color's checker and image     r, g, b
+ *                         texture                 branches: p = o, uv = (d.x, d.y), the
+ *                                                 texture id = the row's int word)
+ * t, t1, t2, face, alpha, beta mean something only where hit / ok is 1.
+ * flags (may be NULL) gets what the host half computed:
+ *   flags[0] 1 when every record is in the shared-reciprocal regime (spheres_fd, prep_quads,
+ *            prep_boxes: the product takes the fd forms only then), 1 for ops without records
+ *   flags[1] RT_OP_BOX: boxes whose 48-byte record is compact (forms 2..4 need all n);
+ *            RT_OP_PERLIN: 1 when the table packs (form 1 needs it)
+ *   flags[2] waves of the batch that hold a row whose a = dot(d, d) is not >= 2^-60 (such a wave
+ *            takes '/' in the fd sphere forms), flags[3] such rows
+ * device < 0: the host half alone (flags), nothing is launched and out is not written.
+ * Returns RT_ERR_INVALID_ARG for a form the records do not allow (a compact form with a box that
+ * is not compact, the packed form with a table that does not pack). */
+enum {
+    RT_OP_SPHERE = 0, RT_OP_MEDIUM_SPHERE, RT_OP_QUAD, RT_OP_BOX, RT_OP_NODE, RT_OP_PERLIN, RT_OP_SPHERE_UV,
+    RT_OP_TEXTURE, RT_OP_N
+};
+#define RT_OPS_ROW_F 12
+#define RT_OPS_OUT_W 8
+int rt_debug_eval_op(int device, int op, int form, const void* recs, size_t rec_bytes, const float* rows, int n,
+                     int tex_format, int tex_w, int tex_h, const void* tex, unsigned int* out, int flags[4]);
+
 /* Host-only: the threaded-BVH re-layout rt_upload_buffer(RT_BIND_BVH) builds
  * (32-byte rt_dnode records); out may be NULL to query the count. */
 int rt_debug_threaded_bvh(const void* nodes, size_t nbytes, void* out, size_t out_cap, int* n_out);

@@ -67,6 +67,15 @@ def lib():
         L.oracle_hit_quad.argtypes = [ctypes.c_void_p, fp, fp, ctypes.c_float, ctypes.c_float, fp, fp, fp,
                                       ctypes.POINTER(ctypes.c_int)]
         L.oracle_hit_aabb.argtypes = [fp, fp, fp, ctypes.c_float, ctypes.c_float]
+        ip = ctypes.POINTER(ctypes.c_int)
+        L.oracle_hit_box.argtypes = [ctypes.c_void_p, fp, fp, ctypes.c_float, ctypes.c_float, fp, ip, fp]
+        L.oracle_medium_boundary_hits.argtypes = [ctypes.c_void_p, ctypes.c_float, fp, fp, fp, fp]
+        L.oracle_texture_bilinear.restype = None
+        L.oracle_texture_bilinear.argtypes = [ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_void_p,
+                                              ctypes.c_float, ctypes.c_float, fp]
+        L.oracle_checker_parity.argtypes = [ctypes.c_float] * 4
+        L.oracle_eval_op.argtypes = [ctypes.c_int, ctypes.c_void_p, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                     ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
         _L = L
     return _L
 
@@ -143,6 +152,120 @@ def rand_sequence(px, py, f, n):
     out = np.empty(n, dtype=np.float32)
     lib().oracle_rand_sequence(px, py, f, n, _fp(out))
     return out
+
+
+# ---- per-operation hooks, array in / array out (rt_debug.h's rt_debug_eval_op layout, so the device's
+# words compare with these directly)
+OPS = {"sphere": 0, "medium_sphere": 1, "quad": 2, "box": 3, "node": 4, "perlin": 5, "sphere_uv": 6, "texture": 7}
+OP_REC_BYTES = {"sphere": 48, "medium_sphere": 48, "quad": 80, "box": 480, "node": 24, "perlin": 0, "sphere_uv": 0,
+                "texture": 0}
+OP_ROW_F, OP_OUT_W = 12, 8
+TEXTYPE_IMAGE, TEXTYPE_CHECKER = 1, 2   # texture.glsl:1-4; a texture id is type << 28 | slot << 12 | detail
+
+
+def op_rows(o, d=None, tmin=0.001, tmax=3.402823e38, time=0.0, word=0):
+    """[n, 12] float32 rows: o, d, tmin, tmax, time, an int word (a texture id), 2 unused."""
+    o = np.asarray(o, np.float32).reshape(-1, 3)
+    n = o.shape[0]
+    rows = np.zeros((n, OP_ROW_F), np.float32)
+    rows[:, 0:3] = o
+    if d is not None:
+        rows[:, 3:6] = np.asarray(d, np.float32).reshape(-1, 3)
+    rows[:, 6], rows[:, 7], rows[:, 8] = tmin, tmax, time
+    rows.view(np.int32)[:, 9] = np.asarray(word, np.int32)
+    return rows
+
+
+def eval_op(op, rows, recs=None, tex=None):
+    """The oracle's result words [n, 8] uint32 of `op` (a name of OPS) over rows ([n, 12] float32); recs:
+    the rows' records as bytes ([n, OP_REC_BYTES[op]] uint8 or any array of that many bytes); tex:
+    (format, w, h, texel array) of slot 0 for the Perlin and texture ops."""
+    rows = np.ascontiguousarray(rows, np.float32)
+    n = rows.shape[0]
+    assert rows.shape == (n, OP_ROW_F)
+    rb = None
+    if OP_REC_BYTES[op]:
+        rb = np.ascontiguousarray(recs).view(np.uint8).reshape(n, OP_REC_BYTES[op])
+    fmt, w, h, texels = tex if tex is not None else (0, 0, 0, None)
+    tb = None if texels is None else np.ascontiguousarray(texels)
+    out = np.zeros((n, OP_OUT_W), np.uint32)
+    rc = lib().oracle_eval_op(OPS[op], None if rb is None else rb.ctypes.data, _fp(rows), n, fmt, w, h,
+                              None if tb is None else tb.ctypes.data,
+                              out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    if rc != 0:
+        raise ValueError(f"oracle_eval_op({op}) failed ({rc})")
+    return out
+
+
+def _f(words):
+    return np.ascontiguousarray(words).view(np.float32)
+
+
+def hit_spheres(spheres, rows):
+    """hit_sphere per row: (hit bool [n], t float32 [n])."""
+    w = eval_op("sphere", rows, spheres)
+    return w[:, 0] != 0, _f(w[:, 1])
+
+
+def medium_boundary_hits(spheres, rows):
+    """hit_constant_medium's two boundary hits on a sphere boundary: (ok, t1, t2)."""
+    w = eval_op("medium_sphere", rows, spheres)
+    return w[:, 0] != 0, _f(w[:, 1]), _f(w[:, 2])
+
+
+def hit_quads(quads, rows):
+    """hit_quad per row: (hit, t, alpha, beta); alpha / beta are hit_record.uv."""
+    w = eval_op("quad", rows, quads)
+    return w[:, 0] != 0, _f(w[:, 1]), _f(w[:, 2]), _f(w[:, 3])
+
+
+def hit_boxes(boxes, rows):
+    """hit_box per row: (hit, t, face, alpha, beta) of the side the record ends with."""
+    w = eval_op("box", rows, boxes)
+    return w[:, 0] != 0, _f(w[:, 1]), w[:, 2].astype(np.int32), _f(w[:, 3]), _f(w[:, 4])
+
+
+def hit_aabbs(box6, rows):
+    return eval_op("node", rows, np.ascontiguousarray(box6, np.float32))[:, 0] != 0
+
+
+def perlin_turbs(table, p):
+    """noise_turb(p, 7) on a [256, 6] float32 table."""
+    t = np.ascontiguousarray(table, np.float32)
+    return _f(eval_op("perlin", op_rows(p), tex=(3, 6, 256, t))[:, 0])
+
+
+def sphere_uvs(p):
+    w = eval_op("sphere_uv", op_rows(p))
+    return _f(w[:, 0]), _f(w[:, 1])
+
+
+def texture_bilinears(fmt, w, h, texels, uv):
+    """texture2D (GL_LINEAR, CLAMP_TO_EDGE) of uv [n, 2]: rgb [n, 3] float32."""
+    uv = np.asarray(uv, np.float32).reshape(-1, 2)
+    d = np.zeros((uv.shape[0], 3), np.float32)
+    d[:, :2] = uv
+    rows = op_rows(np.zeros((uv.shape[0], 3), np.float32), d, word=TEXTYPE_IMAGE << 28)
+    return _f(eval_op("texture", rows, tex=(fmt, w, h, texels))[:, 0:3])
+
+
+def checker_table(scales):
+    """An R32F row of checker textures (even colour 0, odd colour 1, scale), one per entry of scales
+    (at most 4096): detail k of a checker id selects entry k."""
+    s = np.asarray(scales, np.float32).reshape(-1)
+    t = np.zeros((s.size, 3), np.float32)
+    t[:, 1] = 1.0
+    t[:, 2] = s
+    return (3, 3 * s.size, 1, t.reshape(-1))
+
+
+def checker_rows(p, which=0):
+    return op_rows(p, word=(TEXTYPE_CHECKER << 28) | np.asarray(which, np.int32))
+
+
+def checker_parities(scales, p, which=0):
+    """checkerboard()'s parity (0 even, 1 odd) of p [n, 3] under scale scales[which]."""
+    return _f(eval_op("texture", checker_rows(p, which), tex=checker_table(scales))[:, 0]) != 0.0
 
 
 BUILTINS = {"sin": 0, "cos": 1, "log": 2, "acos": 3, "atan2": 4, "fract": 5, "sqrt": 6, "inversesqrt": 7}

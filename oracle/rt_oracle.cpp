@@ -399,12 +399,14 @@ bool hit_quad(const Ray& ray, Interval ray_t, const rt_quad& quad, HitRecord& re
     return true;
 }
 
-bool hit_box(const Ray& ray, Interval ray_t, const rt_box& box, HitRecord& rec) {   // :135-146
+// face (may be NULL; not in the reference): the side whose hit the record holds
+bool hit_box(const Ray& ray, Interval ray_t, const rt_box& box, HitRecord& rec, int* face = nullptr) {   // :135-146
     bool has_hit = false;
     for (int i = 0; i < 6; i++) {
         if (hit_quad(ray, ray_t, box.quads[i], rec)) {
             ray_t.max = rec.t;
             has_hit = true;
+            if (face) *face = i;
         }
     }
     return has_hit;
@@ -426,12 +428,18 @@ bool hit_boundary(Inv& I, const Ray& ray, Interval ray_t, int idx, int type, Hit
     }
 }
 
-bool hit_constant_medium(Inv& I, const Ray& ray, Interval ray_t, const rt_medium& medium, HitRecord& rec) {   // :162-193
-    HitRecord rec1, rec2;
+// :163-169 -- the two boundary hits, before any rand()
+bool medium_boundary_hits(Inv& I, const Ray& ray, const rt_medium& medium, HitRecord& rec1, HitRecord& rec2) {
     if (!hit_boundary(I, ray, Interval{-RT_INFINITY, RT_INFINITY}, medium.boundary_idx, medium.boundary_type, rec1))
         return false;
     if (!hit_boundary(I, ray, Interval{rec1.t + 0.0001f, RT_INFINITY}, medium.boundary_idx, medium.boundary_type, rec2))
         return false;
+    return true;
+}
+
+bool hit_constant_medium(Inv& I, const Ray& ray, Interval ray_t, const rt_medium& medium, HitRecord& rec) {   // :162-193
+    HitRecord rec1, rec2;
+    if (!medium_boundary_hits(I, ray, medium, rec1, rec2)) return false;
     if (rec1.t < ray_t.min) rec1.t = ray_t.min;
     if (rec2.t > ray_t.max) rec2.t = ray_t.max;
     if (rec1.t >= rec2.t) return false;
@@ -979,6 +987,102 @@ int oracle_hit_aabb(const float b[6], const float o[3], const float dir[3], floa
     nd.xmin = b[0]; nd.xmax = b[1]; nd.ymin = b[2]; nd.ymax = b[3]; nd.zmin = b[4]; nd.zmax = b[5];
     Ray r{ld3(o), ld3(dir)};
     return hit_aabb(r, Interval{tmin, tmax}, nd) ? 1 : 0;
+}
+
+int oracle_hit_box(const void* box480, const float o[3], const float dir[3], float tmin, float tmax, float* t,
+                   int* face, float uv[2]) {
+    rt_box b; std::memcpy(&b, box480, sizeof(b));
+    HitRecord rec;
+    Ray r{ld3(o), ld3(dir)};
+    int f = 0;
+    if (!hit_box(r, Interval{tmin, tmax}, b, rec, &f)) return 0;
+    *t = rec.t; *face = f; uv[0] = rec.uv.x; uv[1] = rec.uv.y;
+    return 1;
+}
+
+int oracle_medium_boundary_hits(const void* sphere48, float time, const float o[3], const float dir[3], float* t1,
+                                float* t2) {
+    rt_sphere sp; std::memcpy(&sp, sphere48, sizeof(sp));
+    Scene S; S.spheres = &sp; S.n_spheres = 1;
+    Inv I; I.S = &S; I.C = nullptr; I.time = time;
+    rt_medium m{}; m.boundary_idx = 0; m.boundary_type = RT_MODEL_SPHERE;
+    HitRecord rec1, rec2;
+    Ray r{ld3(o), ld3(dir)};
+    if (!medium_boundary_hits(I, r, m, rec1, rec2)) return 0;
+    *t1 = rec1.t; *t2 = rec2.t;
+    return 1;
+}
+
+void oracle_texture_bilinear(int format, int w, int h, const void* texels, float u, float v, float rgb[3]) {
+    Texture T; T.format = format; T.w = w; T.h = h; T.data = (const uint8_t*)texels;
+    v2 uv = {u, v};
+    v3 c = texture_bilinear(T, uv);
+    rgb[0] = c.x; rgb[1] = c.y; rgb[2] = c.z;
+}
+
+int oracle_checker_parity(float scale, float px, float py, float pz) {
+    // checkerboard() on a 3-texel R32F row (even colour 0, odd colour 1, scale): the colour is the parity
+    const float row[3] = {0.0f, 1.0f, scale};
+    Scene S;
+    S.tex[0].format = RT_TEX_R32F; S.tex[0].w = 3; S.tex[0].h = 1; S.tex[0].data = (const uint8_t*)row;
+    Inv I; I.S = &S; I.C = nullptr;
+    return checkerboard(I, mk3(px, py, pz), 0, 0).x != 0.0f;
+}
+
+// The ops above over n rows in rt_debug_eval_op's layout (include/rt/rt_debug.h: the same op numbers, rows
+// of 12 floats, 8 output words per row, recs as the uploads carry them), so tests compare the device's
+// words with these.  t / alpha / beta / face words stay 0 on a miss.
+int oracle_eval_op(int op, const void* recs, const float* rows, int n, int tex_format, int tex_w, int tex_h,
+                   const void* tex, uint32_t* out) {
+    for (int i = 0; i < n; i++) {
+        const float* r = rows + (size_t)i * 12;
+        uint32_t* w = out + (size_t)i * 8;
+        for (int k = 0; k < 8; k++) w[k] = 0;
+        const float *o = r, *d = r + 3;
+        const float tmin = r[6], tmax = r[7], time = r[8];
+        float t = 0, t2 = 0, p[3], nn[3], uv[2] = {0, 0};
+        int front = 0, face = 0;
+        int32_t word; std::memcpy(&word, r + 9, 4);
+        switch (op) {
+            case 0:
+                w[0] = oracle_hit_sphere((const char*)recs + 48 * (size_t)i, time, o, d, tmin, tmax, &t, p, nn, &front);
+                w[1] = rt_f2u(t);
+                break;
+            case 1:
+                w[0] = oracle_medium_boundary_hits((const char*)recs + 48 * (size_t)i, time, o, d, &t, &t2);
+                w[1] = rt_f2u(t); w[2] = rt_f2u(t2);
+                break;
+            case 2: {
+                rt_quad q; std::memcpy(&q, (const char*)recs + 80 * (size_t)i, sizeof(q));
+                HitRecord rec;
+                Ray ray{ld3(o), ld3(d)};
+                w[0] = hit_quad(ray, Interval{tmin, tmax}, q, rec);
+                if (w[0]) { w[1] = rt_f2u(rec.t); w[2] = rt_f2u(rec.uv.x); w[3] = rt_f2u(rec.uv.y); }
+                break;
+            }
+            case 3:
+                w[0] = oracle_hit_box((const char*)recs + 480 * (size_t)i, o, d, tmin, tmax, &t, &face, uv);
+                w[1] = rt_f2u(t); w[2] = (uint32_t)face; w[3] = rt_f2u(uv[0]); w[4] = rt_f2u(uv[1]);
+                break;
+            case 4: w[0] = oracle_hit_aabb((const float*)recs + 6 * (size_t)i, o, d, tmin, tmax); break;
+            case 5:
+                if (tex_format != RT_TEX_R32F || tex_w != 6 || tex_h != 256) return -1;
+                w[0] = rt_f2u(oracle_perlin_turb((const float*)tex, o[0], o[1], o[2], 7));
+                break;
+            case 6: oracle_get_sphere_uv(o[0], o[1], o[2], &uv[0], &uv[1]); w[0] = rt_f2u(uv[0]); w[1] = rt_f2u(uv[1]); break;
+            case 7: {
+                Scene S;
+                S.tex[0].format = tex_format; S.tex[0].w = tex_w; S.tex[0].h = tex_h; S.tex[0].data = (const uint8_t*)tex;
+                Inv I; I.S = &S; I.C = nullptr; I.time = time;
+                v2 uvv = {d[0], d[1]};
+                v3 c = texture_color(I, ld3(o), word, uvv);
+                w[0] = rt_f2u(c.x); w[1] = rt_f2u(c.y); w[2] = rt_f2u(c.z);
+                break;
+            }
+            default: return -1;
+        }
+    }
+    return 0;
 }
 
 }  // extern "C"

@@ -12,7 +12,9 @@
  * tests or golden vectors.  The oracle is therefore pinned only by (a) the
  * get_sphere_uv known-answer table in texture.glsl:100-102, (b) the std430
  * layout comments of RaytraceModel.java:139-219 vs compute.glsl structs, and
- * (c) statistical agreement with the reference gallery render of scene 6;
+ * (c) statistical agreement with the reference gallery render of scene 6, and
+ * (d) per operation (the oracle_eval_op entry points below) a float64 restatement of the shader
+ * text within derived rounding bounds (tests/ref64.py, tests/test_ops_ref64.py);
  * everything else is "parity unpinned" against the reference itself.
  */
 #ifndef RT_ORACLE_H
@@ -85,6 +87,22 @@ int oracle_hit_sphere(const void* sphere48, float time, const float o[3], const 
 int oracle_hit_quad(const void* quad80, const float o[3], const float dir[3],
                     float tmin, float tmax, float* t, float p[3], float n[3], int* front);
 int oracle_hit_aabb(const float box6[6], const float o[3], const float dir[3], float tmin, float tmax);
+/* hit_box (hitting.glsl:135-146) on 6 rt_quad: t, the side whose hit the record holds, hit_record.uv */
+int oracle_hit_box(const void* box480, const float o[3], const float dir[3], float tmin, float tmax, float* t,
+                   int* face, float uv[2]);
+/* hit_constant_medium's two boundary hits (hitting.glsl:163-169) on a sphere boundary, before any rand():
+ * returns 1 when both hit and fills rec1.t, rec2.t */
+int oracle_medium_boundary_hits(const void* sphere48, float time, const float o[3], const float dir[3], float* t1,
+                                float* t2);
+/* texture2D with GL_LINEAR + CLAMP_TO_EDGE on a texture of rt_types.h format RT_TEX_* */
+void oracle_texture_bilinear(int format, int w, int h, const void* texels, float u, float v, float rgb[3]);
+/* checkerboard()'s parity (texture.glsl:10-11): 0 even (the first colour), 1 odd */
+int oracle_checker_parity(float scale, float px, float py, float pz);
+/* The per-operation hooks over n rows in rt_debug_eval_op's layout (include/rt/rt_debug.h: its op
+ * numbers, rows of 12 floats, 8 output words per row, recs as the uploads carry them; op 7 runs
+ * texture_color on slot 0).  Returns 0, or -1 for an unknown op or a Perlin table of another shape. */
+int oracle_eval_op(int op, const void* recs, const float* rows, int n, int tex_format, int tex_w, int tex_h,
+                   const void* tex, uint32_t* out);
 
 #ifdef __cplusplus
 }

@@ -2,6 +2,7 @@
 // C++, no HIP runtime call and no device, built once and linked into both libraries like rt_prep.cpp.
 // rt_capi.hip's entries call these and then do the device's part; rt_debug_plan_scene
 // (rt_debug_host.cpp) calls the same and reports the result.
+#include <cstddef>
 #include <algorithm>
 #include <climits>
 #include <cmath>
@@ -393,6 +394,8 @@ int scene_args(SceneState& s, rt_kernel_args& a, std::string* err) {
     int32_t lc = 0;
     if (s.host_buf[RT_BIND_LIGHTS].size() >= 4) std::memcpy(&lc, s.host_buf[RT_BIND_LIGHTS].data(), 4);
     a.lights_count = lc;
+    // (tests/test_shading_cases_design.py reads this word from rt_debug_plan_scene's argument block)
+    static_assert(offsetof(rt_kernel_args, uv_always) == 80, "tests read uv_always at byte 80 of rt_kernel_args");
     a.uv_always = s.uv_always;
     a.boxes_canon = s.boxes_canon ? 1 : 0;
     // Box pre-test (rt_kernel.hip leaf_prims_t): a face the exact test accepts lies, with

@@ -8,6 +8,7 @@
 #include <string>
 #include <vector>
 
+#include "rt/rt_glsl.h"
 #include "rt_ctx.h"
 
 using namespace rt_impl;
@@ -31,6 +32,113 @@ int rt_debug_eval_builtin(int device, int fn, const float* x, const float* y, fl
     if (dx) (void)hipFree(dx);
     if (dy) (void)hipFree(dy);
     if (dout) (void)hipFree(dout);
+    return rc;
+}
+
+// The host half prepares the device records with the uploads' own functions (rt_prep.h, rt_args.h) and
+// reports their flags; the device half is rt_ops_eval.hip.
+int rt_debug_eval_op(int device, int op, int form, const void* recs, size_t rec_bytes, const float* rows, int n,
+                     int tex_format, int tex_w, int tex_h, const void* tex, unsigned int* out, int flags[4]) {
+    if (op < 0 || op >= RT_OP_N || form < 0 || !rows || n < 0 || (device >= 0 && !out)) return RT_ERR_INVALID_ARG;
+    static const size_t kRec[RT_OP_N] = {sizeof(rt_sphere), sizeof(rt_sphere), sizeof(rt_quad), 6 * sizeof(rt_quad),
+                                         6 * sizeof(float), 0, 0, 0};
+    static const int kForms[RT_OP_N] = {4, 2, 2, 5, 3, 2, 1, 1};
+    if (form >= kForms[op] || rec_bytes != kRec[op] * (size_t)n || (rec_bytes && !recs)) return RT_ERR_INVALID_ARG;
+    int fl[4] = {1, 0, 0, 0};
+    const int npad = (n + 63) / 64 * 64;
+    // the device records, padded to whole waves with copies of the last row's
+    std::vector<float4> drec;
+    const void* rec_src = nullptr;
+    size_t rec_row = 0;   // bytes per row of what is copied to the device
+    TexturePrep tp;
+    if (op == RT_OP_SPHERE || op == RT_OP_MEDIUM_SPHERE) {
+        fl[0] = spheres_fd((const rt_sphere*)recs, (size_t)n);
+        rec_src = recs;
+        rec_row = sizeof(rt_sphere);
+    } else if (op == RT_OP_QUAD) {
+        fl[0] = prep_quads((const rt_quad*)recs, (size_t)n, drec);
+        rec_src = drec.data();
+        rec_row = RT_DFACE_F4 * sizeof(float4);
+    } else if (op == RT_OP_BOX) {
+        const BoxPrep B = prep_boxes((const rt_quad*)recs, (size_t)n);
+        fl[0] = B.fd;
+        fl[1] = B.n_compact;
+        if (form >= 2 && B.n_compact != n) return RT_ERR_INVALID_ARG;
+        drec.resize((size_t)n * (RT_DBOX_F4 + RT_BOXC_F4));
+        for (int i = 0; i < n; i++) {
+            float4* o = &drec[(size_t)i * (RT_DBOX_F4 + RT_BOXC_F4)];
+            std::copy(&B.faces[(size_t)i * RT_DBOX_F4], &B.faces[(size_t)i * RT_DBOX_F4] + RT_DBOX_F4, o);
+            std::copy(&B.boxc[(size_t)i * RT_BOXC_F4], &B.boxc[(size_t)i * RT_BOXC_F4] + RT_BOXC_F4, o + RT_DBOX_F4);
+        }
+        rec_src = drec.data();
+        rec_row = (RT_DBOX_F4 + RT_BOXC_F4) * sizeof(float4);
+    } else if (op == RT_OP_NODE) {
+        rec_src = recs;
+        rec_row = 6 * sizeof(float);
+    }
+    if (op == RT_OP_PERLIN || op == RT_OP_TEXTURE) {
+        std::string err;
+        if (op == RT_OP_PERLIN && (tex_format != RT_TEX_R32F || tex_w != 6 || tex_h != 256)) return RT_ERR_INVALID_ARG;
+        const int r = prep_texture(0, tex_format, tex_w, tex_h, tex, tp, &err);
+        if (r) return r;
+        fl[1] = op == RT_OP_PERLIN && !tp.pk.empty();
+        if (op == RT_OP_PERLIN && form == 1 && tp.pk.empty()) return RT_ERR_INVALID_ARG;
+    }
+    for (int w = 0; w < npad / 64; w++) {
+        int bad = 0;
+        for (int i = w * 64; i < w * 64 + 64; i++) {
+            const float* r = rows + (size_t)std::min(i, n - 1) * RT_OPS_ROW_F;
+            const float a = g_dot(mk3(r[3], r[4], r[5]), mk3(r[3], r[4], r[5]));
+            if (!(a >= 0x1p-60f)) bad += i < n;
+        }
+        fl[2] += bad > 0;
+        fl[3] += bad;
+    }
+    if (flags) std::memcpy(flags, fl, sizeof(fl));
+    if (device < 0 || n == 0) return RT_OK;
+
+    if (hipSetDevice(device) != hipSuccess) return RT_ERR_DEVICE;
+    void *d_rec = nullptr, *d_rows = nullptr, *d_out = nullptr, *d_tex = nullptr, *d_args = nullptr;
+    const size_t rows_b = (size_t)npad * RT_OPS_ROW_F * sizeof(float), out_b = (size_t)npad * RT_OPS_OUT_W * 4;
+    int rc = RT_OK;
+    auto up = [&](void** d, const void* src, size_t row, size_t bytes_dev) {   // rows 0..n-1, then the last row again
+        if (rc || !bytes_dev) return;
+        if (hipMalloc(d, bytes_dev) != hipSuccess) { rc = RT_ERR_DEVICE; return; }
+        if (hipMemcpy(*d, src, row * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_DEVICE;
+        for (int i = n; i < npad && !rc; i++)
+            if (hipMemcpy((char*)*d + row * (size_t)i, (const char*)src + row * (size_t)(n - 1), row,
+                          hipMemcpyHostToDevice) != hipSuccess)
+                rc = RT_ERR_DEVICE;
+    };
+    up(&d_rows, rows, RT_OPS_ROW_F * sizeof(float), rows_b);
+    if (rec_row) up(&d_rec, rec_src, rec_row, rec_row * (size_t)npad);
+    if (!rc && hipMalloc(&d_out, out_b) != hipSuccess) rc = RT_ERR_DEVICE;
+    if (!rc && hipMemset(d_out, 0, out_b) != hipSuccess) rc = RT_ERR_DEVICE;
+    // the argument block the texture functions read: slot 0's texture in global memory, no LDS tables
+    rt_kernel_args* a = new rt_kernel_args();
+    std::memset(a, 0, sizeof(*a));
+    a->perlin_slot = a->perlin_lds = a->media_lds = a->sph_lds = a->sph_mat_lds = a->box_mat_lds = a->tex_lds =
+        a->box_cmp_lds = a->leaf_lds = -1;
+    if (op == RT_OP_PERLIN || op == RT_OP_TEXTURE) {
+        const bool pk = op == RT_OP_PERLIN && form == 1;
+        const void* src = pk ? (const void*)tp.pk.data() : tp.src;
+        const size_t b = pk ? tp.pk.size() * sizeof(float4) : tp.bytes;
+        if (!rc && hipMalloc(&d_tex, b) != hipSuccess) rc = RT_ERR_DEVICE;
+        if (!rc && hipMemcpy(d_tex, src, b, hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_DEVICE;
+        a->tex[0].data = d_tex;
+        a->tex[0].w = tex_w;
+        a->tex[0].h = tex_h;
+        a->tex[0].is_float = tex_format == RT_TEX_R32F;
+    }
+    if (!rc && hipMalloc(&d_args, sizeof(*a)) != hipSuccess) rc = RT_ERR_DEVICE;
+    if (!rc && hipMemcpy(d_args, a, sizeof(*a), hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_DEVICE;
+    delete a;
+    if (!rc && rt_launch_eval_op((const rt_kernel_args*)d_args, op, form, op == RT_OP_PERLIN ? d_tex : d_rec,
+                                 (const float*)d_rows, d_out, npad, nullptr))
+        rc = RT_ERR_DEVICE;
+    if (!rc && hipMemcpy(out, d_out, (size_t)n * RT_OPS_OUT_W * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = RT_ERR_DEVICE;
+    for (void* p : {d_rec, d_rows, d_out, d_tex, d_args})
+        if (p) (void)hipFree(p);
     return rc;
 }
 

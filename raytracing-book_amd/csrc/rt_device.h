@@ -261,3 +261,6 @@ int rt_launch_deinterleave(const void* gathered, void* out, int width, int heigh
                            int padded_rows, void* stream);
 // debug: evaluate GLSL built-ins on device (tests)
 int rt_launch_eval_builtin(int fn, const float* dx, const float* dy, float* dout, int n, void* stream);
+// debug: evaluate the kernels' own operations (rt_debug.h rt_debug_eval_op; rt_ops_eval.hip); n a multiple of 64
+int rt_launch_eval_op(const rt_kernel_args* dargs, int op, int form, const void* drecs, const float* drows, void* dout,
+                      int n, void* stream);

@@ -197,6 +197,9 @@ def _amd_protos(L, old_rev=False):
         _proto(L, "rt_debug_plan_scene", i, ctypes.POINTER(RtDebugSceneIn), ctypes.POINTER(RtDebugSceneOut))
     if not old_rev or hasattr(L, "rt_debug_first_leaf"):   # ... or from before the first-leaf prologue
         _proto(L, "rt_debug_first_leaf", i, vp, c_int_p)
+    if not old_rev or hasattr(L, "rt_debug_eval_op"):   # ... or from before the per-operation evaluator
+        _proto(L, "rt_debug_eval_op", i, i, i, i, vp, sz, c_float_p, i, i, i, i, vp, ctypes.POINTER(ctypes.c_uint32),
+               c_int_p)
     _proto(L, "rt_set_bvh_mode", i, vp, i)
     _proto(L, "rt_debug_walk_bvh", i, vp, vp, sz, ctypes.POINTER(sz))
     _proto(L, "rt_debug_build_sah_bvh", i, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, i, c_float_p, f, vp, sz,
@@ -293,3 +296,27 @@ def scene_lib():
         _proto(L, "rts_finish", i, vp, i, i)
         _scene = L
     return _scene
+
+
+def debug_eval_op(op, form, rows, recs=None, tex=None, device=0, lib=None):
+    """rt_debug_eval_op (rt_debug.h): the render kernels' own operation `op` in device form `form` over
+    rows ([n, 12] float32), one lane per row.  recs: the rows' records as the uploads carry them (any
+    array of n records' bytes); tex: (format, w, h, texel array) for the Perlin and texture ops.
+    Returns (words [n, 8] uint32, flags [4] ints); device < 0 runs the host half alone (flags)."""
+    import numpy as np
+    L = lib or amd()
+    rows = np.ascontiguousarray(rows, np.float32)
+    n = rows.shape[0]
+    if rows.shape != (n, 12):
+        raise ValueError("rows must be [n, 12] float32")
+    rb = None if recs is None else np.ascontiguousarray(recs).view(np.uint8).reshape(-1)
+    fmt, w, h, texels = tex if tex is not None else (0, 0, 0, None)
+    tb = None if texels is None else np.ascontiguousarray(texels)
+    out = np.zeros((n, 8), np.uint32)
+    flags = (ctypes.c_int * 4)()
+    rc = L.rt_debug_eval_op(device, op, form, None if rb is None else rb.ctypes.data, 0 if rb is None else rb.size,
+                            rows.ctypes.data_as(c_float_p), n, fmt, w, h, None if tb is None else tb.ctypes.data,
+                            out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)), flags)
+    if rc != 0:
+        raise RTError(rc, f"rt_debug_eval_op(op {op}, form {form})")
+    return out, list(flags)

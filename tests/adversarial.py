@@ -24,6 +24,8 @@ hit tests they target (hitting.glsl:90-146):
     grid; and near an edge of the box.
 Secondary bounces add random rays around the same geometry.
 """
+import os
+
 import numpy as np
 
 import rtamd
@@ -248,4 +250,125 @@ def cases():
         Case("spine_face_0.01", spine(0.01)),
         Case("spine_edge_0.0019", spine(0.0019, corner=True)),
         Case("spine_jitter", spine(0.0019), spp=16, frames=4),
+    ]
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Shading cases: light sampling, the media tables, stale and lazy uv -- what no pure per-ray operation
+# covers (tests/test_gpu_shading_cases.py, tests/test_shading_cases_design.py).  Kept apart from cases():
+# its CPU test asserts every pixel finite, and light_inside is built to produce NaN.
+GOLD = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
+
+
+def lights_many(W=64, H=48):
+    """Three quad lights -- one edge-on to part of the floor -- and two sphere lights, one of them moving
+    (center2), over lambertian receivers and a thin fog: lights_random / lights_pdf_value over five lights."""
+    b = SceneBuilder(seed=1)
+    white, red, light = _materials(b)
+    b.add(b.quad((-6, -2, -16), (12, 0, 0), (0, 0, 14), white))            # the floor y = -2
+    b.add(b.quad((-6, -2, -16), (12, 0, 0), (0, 8, 0), red))               # a back wall
+    b.add(b.sphere((0, -1, -9), 1.0, white))
+    for q, u, v in (((-3, 4, -12), (2, 0, 0), (0, 0, 2)),                   # overhead
+                    ((2, 4, -8), (2, 0, 0), (0, 0, 2)),
+                    ((-5, -2, -10), (0, 3, 0), (0, 0, 2))):                 # upright on the floor: edge-on to it
+        b.add_light(b.add(b.quad(q, u, v, light)))
+    b.add_light(b.add(b.sphere((3, 1, -11), 0.5, light)))
+    b.add_light(b.add(b.sphere((-2, 2, -7), 0.4, light, center2=(-1, 2.5, -7))))
+    fog = b.sphere((0, -0.5, -9), 2.0, b.dielectric(1.5))                   # clear of the sphere lights: no scatter inside one
+    b.add(b.constant_medium(fog, 0.1, b.isotropic(b.solid(0.8, 0.8, 0.9))))
+    b.camera(look_from=(0, 1, 2), look_at=(0, 0, -9), vfov=50, background=(0.02, 0.02, 0.03))
+    return b.finish(W, H)
+
+
+def light_inside(W=48, H=32):
+    """A registered glass sphere light with a lambertian quad cutting through it: shading points on the
+    quad inside the sphere sample it from within, where rand_to_sphere's sqrt(1 - r^2 / d^2) is NaN (Q11)."""
+    b = SceneBuilder(seed=1)
+    white, red, light = _materials(b)
+    b.add(b.quad((-4, -1, -10), (8, 0, 0), (0, 0, 8), white))              # y = -1 through the sphere
+    b.add_light(b.add(b.sphere((0, -1, -6), 2.0, b.dielectric(1.5))))
+    b.add_light(b.add(b.quad((-1, 4, -7), (2, 0, 0), (0, 0, 2), light)))
+    b.camera(look_from=(0, 2, 0), look_at=(0, -1, -6), vfov=60, background=(0.3, 0.3, 0.3))
+    return b.finish(W, H)
+
+
+def media_box_all_compact(W=64, H=48):
+    """Canonical boxes only, one of them a medium's boundary: media_sph = 0 in a compact-box kernel."""
+    b = SceneBuilder(seed=1)
+    white, red, light = _materials(b)
+    b.add(b.box((-6, -3, -16), (6, -2, -2), white))
+    b.add(b.box((-3, -2, -9), (-1, 0, -7), red))
+    fog = b.box((0, -2, -10), (3, 1, -6), white)
+    b.add(b.constant_medium(fog, 0.6, b.isotropic(b.solid(0.9, 0.9, 0.9))))
+    b.add_light(b.add(b.quad((-2, 4, -10), (4, 0, 0), (0, 0, 4), light)))
+    b.camera(look_from=(0, 0.5, 1), look_at=(0.5, -0.5, -8), vfov=55, background=(0.2, 0.25, 0.3))
+    return b.finish(W, H)
+
+
+def media_many(n, W=48, H=32):
+    """n small sphere-bounded fogs in a grid: 64 still stage their records in LDS, 65 read them from
+    global memory (rt_plan.cpp plan_lds)."""
+    b = SceneBuilder(seed=1)
+    white, red, light = _materials(b)
+    b.add(b.quad((-8, -2, -20), (16, 0, 0), (0, 0, 18), white))
+    for k in range(n):
+        x, z = -5.5 + 1.0 * (k % 12), -6.0 - 1.6 * (k // 12)
+        fog = b.sphere((x, -0.5 + 0.25 * (k % 3), z), 0.45, b.dielectric(1.5))
+        b.add(b.constant_medium(fog, 1.5 + 0.5 * (k % 4), b.isotropic(b.solid(0.9, 0.6 + 0.05 * (k % 5), 0.5))))
+    b.add_light(b.add(b.quad((-3, 5, -14), (6, 0, 0), (0, 0, 6), light)))
+    b.camera(look_from=(0, 3, 2), look_at=(0, -0.5, -10), vfov=50, background=(0.3, 0.35, 0.4))
+    return b.finish(W, H)
+
+
+def media_image_texture(W=64, H=48):
+    """An isotropic medium with an image texture behind an image-textured sphere and quad: a fog scatter
+    reads the uv the last sphere or quad hit of the sample left (Q9), so uv_always is set."""
+    b = SceneBuilder(seed=1)
+    white, red, light = _materials(b)
+    rgba = b.image(os.path.join(GOLD, "tex_rgba.png"), 0, 0)
+    jpg = b.image(os.path.join(GOLD, "tex_progressive.jpg"), 0, 0)
+    b.add(b.sphere((-1.5, 0, -5), 1.0, b.lambertian(jpg)))
+    b.add(b.quad((0.5, -1, -5), (2, 0, 0), (0, 2, 0), b.lambertian(rgba)))
+    b.add(b.sphere((0, 0, -3), 0.6, b.dielectric(1.5)))                     # glass in front: paths go on to the fog
+    fog = b.sphere((0, 0, -9), 3.0, b.dielectric(1.5))
+    b.add(b.constant_medium(fog, 0.8, b.isotropic(rgba)))
+    b.add_light(b.add(b.quad((-2, 5, -8), (4, 0, 0), (0, 0, 4), light)))
+    b.camera(look_from=(0, 0, 1), look_at=(0, 0, -6), vfov=60, background=(0.4, 0.45, 0.5))
+    return b.finish(W, H)
+
+
+def textures_edges(W=64, H=48):
+    """A grid camera whose rays d = (-2 + x / 16, 1.5 - y / 16, -1) meet the image-textured quad
+    (-1, -0.5, -4) + a (2, 0, 0) + b (0, 1, 0) at alpha / beta exactly 0 and 1 (4 d.x = -1, 1: columns 28 and
+    36; 4 d.y = 0.5, -0.5: rows 22 and 26) and the checker floor y = -2, spanning negative x, on cell
+    boundaries: its scale 1 is stored as the byte 255, so 1 / scale = 1 and the cells are the unit squares --
+    y = -2 is itself a boundary, and rows 28, 32 and 40 (d.y = -1/4, -1/2, -1: t = 8, 4, 2) land on whole z and,
+    every 2nd, 4th and 8th column, whole x.  A Perlin sphere; an image-textured moving sphere (its uv
+    resolved lazily at time)."""
+    b = SceneBuilder(seed=1)
+    white, red, light = _materials(b)
+    rgba = b.image(os.path.join(GOLD, "tex_rgba.png"), 5, 3)
+    jpg = b.image(os.path.join(GOLD, "tex_progressive.jpg"), 0, 0)
+    b.add(b.quad((-1, -0.5, -4), (2, 0, 0), (0, 1, 0), b.lambertian(rgba)))
+    b.add(b.quad((-8, -2, -16), (16, 0, 0), (0, 0, 16), b.lambertian(b.checker((0.1, 0.2, 0.1), (0.9, 0.9, 0.9), 1.0))))
+    b.add(b.sphere((-2.5, 0.5, -6), 1.0, b.lambertian(b.perlin(4.0))))
+    b.add(b.sphere((2.5, 0.5, -6), 0.9, b.lambertian(jpg), center2=(2.5, 1.0, -6)))
+    b.add_light(b.add(b.quad((-2, 5, -8), (4, 0, 0), (0, 0, 4), light)))
+    b.camera(background=(0.5, 0.55, 0.6))
+    s = b.finish(W, H)
+    s.override_camera(grid_camera((0, 0, 0), (-2 + 1 / 32, 1.5 - 1 / 32, -1), (1 / 16, 0, 0), (0, -1 / 16, 0)))
+    return s
+
+
+def shading_cases():
+    """Each at most 64 x 48, 4 frames, depth 5.  expect: rt_debug_last_launch fields of the default render;
+    pk: rt_debug_plan_scene's RT_PK_* inputs (name -> predicate), uv_always: the argument block's word."""
+    return [
+        Case("lights_many", lights_many(), frames=4, depth=5, spp=4),
+        Case("light_inside", light_inside(), frames=4, depth=5, spp=4),
+        Case("media_box_all_compact", media_box_all_compact(), frames=4, depth=5, spp=4, expect={"box_records": 3}),
+        Case("media_64", media_many(64), frames=3, depth=4, spp=4),
+        Case("media_65", media_many(65), frames=3, depth=4, spp=4),
+        Case("media_image_texture", media_image_texture(), frames=4, depth=5, spp=4),
+        Case("textures_edges", textures_edges(), frames=3, depth=4),
     ]
