@@ -327,6 +327,67 @@ int rt_read_denoised(rt_ctx* ctx, float* rgba);
 int rt_denoise_host(const float* image, const float* m2, const int32_t* tile_frames, int n_tiles,
                     int width, int height, const rt_denoise_params* params, float* rgba_out);
 
+/* ---- First-hit feature buffers, and their use as guides of the preview filter -------------------
+ * rt_render_features traces one deterministic ray per pixel (x, y) and keeps what it hits first:
+ *   coord = (up_left + pixel_delta_u * (float)x) + pixel_delta_v * (float)y   (rt_render's pixel base),
+ *   o = camera_pos, d = coord - o, time 0, ray_t = (0.001, RT_INFINITY):
+ * the pixel's centre ray through a pinhole at camera_pos -- no jitter, no defocus disk, no rand() draw;
+ * the buffers depend on the scene and the camera alone.  The closest hit is the one rt_render's first
+ * walk finds for that ray with the constant media left out: the walk runs over the current BVH
+ * (rt_set_bvh_mode), tests the leaves in walk order with the render's own leaf tests, each accepted
+ * hit shrinking ray_t.max (ties resolve as in the render), and skips every leaf slot of type
+ * RT_MODEL_CONSTANT_MEDIUM (a medium's hit draws rand()); a primitive that is only a medium's boundary
+ * is in no leaf and is not hit.  Two float4 buffers in the image's layout (row 0 = top):
+ *   normal_depth = (N.x, N.y, N.z, t): N the shading normal as the render forms it at p = o + d * t
+ *     (sphere: (p - center) / radius; quad or box face: the record's normal; negated when
+ *     dot(d, N) >= 0), t the accepted hit's t in units of |d|;
+ *   albedo_id = (A.r, A.g, A.b, id): A the attenuation the first bounce multiplies in, the material's
+ *     texture at p with this hit's uv at time 0 -- for RT_MAT_DIFFUSE_LIGHT the emission on a
+ *     front-face hit and (0, 0, 0) on a back-face hit; id holds the bits of a uint32:
+ *     prim type | box face << 4 | prim index << 16.
+ * A miss stores N = 0, t = -1, A = the background colour (rt_set_params), id = RT_FEATURE_MISS.
+ *
+ * The buffers (32 bytes per pixel, allocated by the first rt_render_features; a context that never
+ * calls it allocates and runs nothing new) hold the result until rt_upload_buffer, rt_upload_texture,
+ * rt_set_camera, rt_set_bvh_mode (stale: RT_ERR_STATE from the readers until the next
+ * rt_render_features), rt_resize (freed) or rt_destroy.  rt_set_params does not make them stale: a
+ * miss keeps the background of the pass.  Image, moments and frame counts are never touched.
+ * Single-device contexts without rt_set_partition (RT_ERR_STATE otherwise). */
+#define RT_FEATURE_MISS 0xFFFFFFFFu
+/* Queue the pass on the context's stream.  RT_ERR_STATE without BVH, camera or rt_resize. */
+int rt_render_features(rt_ctx* ctx);
+/* rt_sync, then W*H*4 floats each; either pointer may be NULL.  RT_ERR_STATE while none is held. */
+int rt_read_features(rt_ctx* ctx, float* normal_depth, float* albedo_id);
+
+/* The guided filter: rt_denoise's filter with one more factor g on each tap's weight, from the
+ * feature buffers; the same rules (f32, no contraction, only + - * / sqrtf fabsf g_max).  A pixel is
+ * guide-good when its N, t and A are all finite; hit(p) means id(p) != RT_FEATURE_MISS.  For a tap q
+ * of pixel p (both good in rt_denoise's sense):
+ *   g = 1                  if p or q is not guide-good
+ *   g = 0                  else if hit(p) != hit(q)
+ *   g = (gn * gz) * ga     otherwise, where a term whose k is exactly 0 is exactly 1, and
+ *     gn = 1 for two misses, else g_max(0, 1 - kn * (1 - ((N_p.x*N_q.x + N_p.y*N_q.y) + N_p.z*N_q.z)))
+ *     gz = 1 for two misses, else g_max(0, 1 - kz * (fabsf(t_p - t_q) / (g_max(t_p, t_q) + 1e-30f)))
+ *     ga = g_max(0, 1 - ka * ((fabsf(A_p.x-A_q.x) + fabsf(A_p.y-A_q.y)) + fabsf(A_p.z-A_q.z)))
+ *   w = ((h[dy] * h[dx]) * g_max(0, 1 - d)) * g
+ * and everything else as in rt_denoise (Vb, the sums, den, the variance update, skipped taps, bad
+ * pixels).  The guides are the same at every level.  With kn = kz = ka = 0 no guide applies (g = 1 on
+ * every tap, the hit / miss rule included) and the result is rt_denoise's bit for bit.
+ * Each k is finite and >= 0, reserved 0 (RT_ERR_INVALID_ARG otherwise); NULL = the defaults below,
+ * the setting that tools/denoise_quality.py's grid found best on scene 0 among those no worse than
+ * the unguided filter on scenes 8, 6 and 2 (profiles/denoise_guided_quality.json). */
+#define RT_GUIDE_DEFAULT_KN 0.5f
+#define RT_GUIDE_DEFAULT_KZ 1.0f
+#define RT_GUIDE_DEFAULT_KA 1.0f
+typedef struct rt_guide_params { float kn, kz, ka; int reserved[5]; /* must be 0 */ } rt_guide_params;
+/* rt_denoise with the guides: its preconditions, plus feature buffers held (RT_ERR_STATE naming
+ * rt_render_features otherwise).  The result is read with rt_read_denoised. */
+int rt_denoise_guided(rt_ctx* ctx, const rt_denoise_params* params, const rt_guide_params* guides);
+/* Host only: rt_denoise_host with the guides; normal_depth / albedo_id: W*H*4 floats each. */
+int rt_denoise_guided_host(const float* image, const float* m2, const int32_t* tile_frames, int n_tiles,
+                           const float* normal_depth, const float* albedo_id, int width, int height,
+                           const rt_denoise_params* params, const rt_guide_params* guides, float* rgba_out);
+
 /* Per-frame u_rand_factor for frame index f (0-based) of a seeded render:
  * top 24 bits of splitmix64(seed, f) / 2^24, in [0,1).  Stands in for the
  * reference's (float)Math.random() per frame (RaytraceExecutor.java:124). */

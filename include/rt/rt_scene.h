@@ -103,6 +103,8 @@ void rts_spp_uniforms(int spp, float* sqrt_spp, float* recip_sqrt_spp);
  * -> (byte)(pow(b/255, 1/2.2)*255) -> RGB PNG.  rgb8_out (W*H*3) optional. */
 int rts_tonemap_rgb8(const float* rgba, int width, int height, uint8_t* rgb8_out);
 int rts_save_png(const float* rgba, int width, int height, const char* path);
+/* The same PNG writer over bytes as given (W*H*3, row 0 = top): no tonemap (data images). */
+int rts_save_png_rgb8(const uint8_t* rgb8, int width, int height, const char* path);
 
 /* ImageTexture.create's read (ImageTexture.java:22-85: ImageIO.read, then getRGB per
  * pixel): decode a JPEG (baseline / progressive, the IJG decoder's islow IDCT, fancy

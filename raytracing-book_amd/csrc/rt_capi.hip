@@ -129,6 +129,7 @@ int rt_destroy(rt_ctx* c) {
         dev_free(d.gather); dev_free(d.full); dev_free(d.perlin_pk); dev_free(d.sflags);
         dev_free(d.m2); dev_free(d.tile_sums); dev_free(d.node_hits); dev_free(d.tile_list);
         dev_free(d.dn_px[0]); dev_free(d.dn_px[1]); dev_free(d.dn_vb); dev_free(d.dn_counts);
+        dev_free(d.ft_nd); dev_free(d.ft_ai); dev_free(d.ft_links); dev_free(d.ft_args);
         comm_destroy(d);
         if (d.ring) (void)hipHostFree(d.ring);
         for (auto& e : d.ring_ev)
@@ -149,6 +150,7 @@ int rt_upload_buffer(rt_ctx* c, int binding, const void* bytes, size_t nbytes) {
     BufferPrep p;
     int r = prep_buffer(*c, binding, bytes, nbytes, p, &c->err);
     if (r) return r;
+    c->ft_valid = c->ft_links_ok = false;   // the first-hit buffers are another scene's now
     for (Device& d : c->devs) {
         DevBuf* b = nullptr;
         switch (binding) {
@@ -179,6 +181,7 @@ int rt_upload_texture(rt_ctx* c, int slot, int format, int w, int h, const void*
     TexturePrep p;
     int r = prep_texture(slot, format, w, h, texels, p, &c->err);
     if (r) return r;
+    c->ft_valid = false;   // the first-hit albedo was another texture's
     for (Device& d : c->devs) {
         r = dev_alloc_copy(c, d, d.tex[slot], p.src, p.bytes);
         if (r) return r;
@@ -194,6 +197,7 @@ int rt_upload_texture(rt_ctx* c, int slot, int format, int w, int h, const void*
 int rt_set_camera(rt_ctx* c, const float ubo[28]) {
     if (!c || !ubo) return set_err(c, RT_ERR_INVALID_ARG, "NULL camera");
     set_camera(*c, ubo);
+    c->ft_valid = c->ft_links_ok = false;   // the first-hit buffers were another camera's (and under RT_BVH_SAH another tree's)
     return RT_OK;
 }
 
@@ -234,6 +238,7 @@ int rt_resize(rt_ctx* c, int w, int h) {
     }
     c->staged_frames = 0;
     denoise_free(c);        // (alloc_image left every stream idle) the filtered image was the old size's
+    features_free(c);       // ... and so were the first-hit buffers
     set_all_frames(c, 0);   // another image: no tile holds a frame, and a tile mask no longer fits it
     c->mask_set = false;
     c->act_list.clear();
@@ -781,6 +786,7 @@ int rt_set_bvh_mode(rt_ctx* c, int mode) {
     if (mode != RT_BVH_REFERENCE && mode != RT_BVH_SAH) return set_err(c, RT_ERR_INVALID_ARG, "bad BVH mode");
     if (mode != c->bvh_mode) {
         c->bvh_mode = mode;
+        c->ft_valid = c->ft_links_ok = false;   // the first-hit pass walked the other tree
         c->validated = false;   // validate() rebuilds the links (and a new fast_gen re-uploads them)
     }
     return RT_OK;

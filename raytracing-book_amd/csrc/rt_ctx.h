@@ -1,5 +1,5 @@
 // rt_ctx.h — the context behind the C ABI's rt_ctx handle and the device helpers its
-// translation units share (rt_capi.hip, rt_comm.hip, rt_debug.hip).  Internal to the libraries.
+// translation units share (rt_capi.hip, rt_comm.hip, rt_debug.hip, rt_denoise.hip, rt_features.hip).  Internal to the libraries.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -50,6 +50,9 @@ struct Device {
     DevBuf dn_px[2];         // rt_denoise: the levels' ping-pong {r, g, b, V} float4 per pixel (rt_denoise.hip) ...
     DevBuf dn_vb;            // ... the level's 3x3-averaged variance, one float per pixel ...
     DevBuf dn_counts;        // ... and the per-tile frame counts (int32, rt_ctx::dn_counts holds the same)
+    DevBuf ft_nd, ft_ai;     // rt_render_features: normal_depth and albedo_id, float4 [local_rows][W] each (rt_features.hip) ...
+    DevBuf ft_links;         // ... the pass's plain link buffer (SceneState::links) ...
+    DevBuf ft_args;          // ... and its own rt_kernel_args (no LDS tables; rt_ctx::ft_args_host holds the same)
     DevBuf wbuf;             // pooled units (ordered / one chunk): per resident wave 64 x chunk_frames colours
     DevBuf finfo;            // exact near-first walk tables (variant 61)
     DevBuf f2inner, f2leaves;
@@ -86,6 +89,11 @@ struct rt_ctx : rt_impl::SceneState {
     // counts last copied to Device::dn_counts (copied again only when they change)
     int dn_result = -1;
     std::vector<int32_t> dn_counts;
+    // rt_render_features: the buffers hold the current scene's and camera's first hits (false: none held,
+    // or stale since an upload, a camera or a BVH-mode change); ft_links_ok: Device::ft_links holds the
+    // current tree's links (cleared with ft_valid); the argument block last copied to Device::ft_args
+    bool ft_valid = false, ft_links_ok = false;
+    std::vector<uint8_t> ft_args_host;
     // the first device's staged colours of the last launch (rt_debug_read_samples): frames, sparse flags
     int staged_frames = 0;
     bool staged_sparse = false;

@@ -7,7 +7,8 @@
 // from global memory at every step (the caches serve the reuse between neighbours; an LDS tile with
 // halo for steps 1 and 2 measured no faster, the level being bound by its 24 divisions and square
 // roots per pixel: DESIGN.md §4).  The arithmetic is rt_denoise_math.h's, shared with the host
-// reference, which the result equals bit for bit.
+// reference, which the result equals bit for bit.  rt_denoise_guided runs the same passes with
+// dn_filter_guided_kernel, whose taps also read the first-hit buffers (rt_features.hip) for the guide factor.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -53,6 +54,18 @@ __global__ void __launch_bounds__(256) dn_filter_kernel(const rt_dn4* __restrict
     dst[(size_t)y * W + x] = o;
 }
 
+// rt_denoise_guided's level: the same taps, each weight times dn_guide_weight of the first-hit buffers
+template <bool FINAL>
+__global__ void __launch_bounds__(256) dn_filter_guided_kernel(const rt_dn4* __restrict__ src, const float* __restrict__ vb,
+                                                               rt_dn4* __restrict__ dst, int W, int H, int s, float k,
+                                                               rt_dn_guides G) {
+    const int x = (int)blockIdx.x * kBX + (int)threadIdx.x, y = (int)blockIdx.y * kBY + (int)threadIdx.y;
+    if (x >= W || y >= H) return;
+    rt_dn4 o = dn_filter_guided(src, vb, W, H, x, y, s, k, G);
+    if (FINAL) o.w = 1.0f;
+    dst[(size_t)y * W + x] = o;
+}
+
 }  // namespace
 
 namespace rt_impl {
@@ -72,10 +85,10 @@ void denoise_free(rt_ctx* c) {
 
 using namespace rt_impl;
 
-extern "C" {
+namespace {
 
-int rt_denoise(rt_ctx* c, const rt_denoise_params* params) {
-    if (!c) return RT_ERR_INVALID_ARG;
+// rt_denoise (guides NULL) and rt_denoise_guided (the resolved strengths; all 0: the unguided kernels)
+int run_denoise(rt_ctx* c, const rt_denoise_params* params, const rt_guide_resolved* guides) {
     rt_dn_resolved prm;
     if (denoise_resolve(params, &prm))
         return set_err(c, RT_ERR_INVALID_ARG, "rt_denoise: levels 1..5, k > 0 and finite, reserved 0");
@@ -85,6 +98,9 @@ int rt_denoise(rt_ctx* c, const rt_denoise_params* params) {
     if (!c->moments) return set_err(c, RT_ERR_STATE, "rt_set_moments(ctx, 1) first");
     Device& d = c->devs[0];
     if (!d.m2.ptr || !d.image_ptr) return set_err(c, RT_ERR_STATE, "no image");
+    if (guides && !(c->ft_valid && d.ft_nd.ptr && d.ft_ai.ptr))
+        return set_err(c, RT_ERR_STATE, "rt_denoise_guided: no first-hit features held (rt_render_features first)");
+    const bool guided = guides && dn_guides_on(*guides);
     if (c->moments_frames < 2)   // the smallest tile count (rt_ctx.h)
         return set_err(c, RT_ERR_STATE,
                        c->moments_frames < 1 ? "the moments are invalid: render from frame 1 (or rt_write_moments)"
@@ -113,9 +129,17 @@ int rt_denoise(rt_ctx* c, const rt_denoise_params* params) {
     hipLaunchKernelGGL(dn_prologue_kernel, grid, block, 0, d.stream, (const rt_dn4*)d.image_ptr, (const rt_dn4*)d.m2.ptr,
                        (const int32_t*)d.dn_counts.ptr, W, H, buf[0]);
     int cur = 0;
+    rt_dn_guides G = {nullptr, nullptr, 0.0f, 0.0f, 0.0f};
+    if (guided) G = {(const rt_dn4*)d.ft_nd.ptr, (const rt_dn4*)d.ft_ai.ptr, guides->kn, guides->kz, guides->ka};
     for (int lv = 0; lv < prm.levels; lv++, cur ^= 1) {
         hipLaunchKernelGGL(dn_vb_kernel, grid, block, 0, d.stream, (const rt_dn4*)buf[cur], (float*)d.dn_vb.ptr, W, H);
-        if (lv + 1 == prm.levels)
+        if (guided && lv + 1 == prm.levels)
+            hipLaunchKernelGGL(dn_filter_guided_kernel<true>, grid, block, 0, d.stream, (const rt_dn4*)buf[cur],
+                               (const float*)d.dn_vb.ptr, buf[cur ^ 1], W, H, 1 << lv, prm.k, G);
+        else if (guided)
+            hipLaunchKernelGGL(dn_filter_guided_kernel<false>, grid, block, 0, d.stream, (const rt_dn4*)buf[cur],
+                               (const float*)d.dn_vb.ptr, buf[cur ^ 1], W, H, 1 << lv, prm.k, G);
+        else if (lv + 1 == prm.levels)
             hipLaunchKernelGGL(dn_filter_kernel<true>, grid, block, 0, d.stream, (const rt_dn4*)buf[cur],
                                (const float*)d.dn_vb.ptr, buf[cur ^ 1], W, H, 1 << lv, prm.k);
         else
@@ -126,6 +150,23 @@ int rt_denoise(rt_ctx* c, const rt_denoise_params* params) {
     if (e != hipSuccess) return set_err(c, RT_ERR_DEVICE, std::string("rt_denoise launch failed: ") + hipGetErrorString(e));
     c->dn_result = cur;
     return RT_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int rt_denoise(rt_ctx* c, const rt_denoise_params* params) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    return run_denoise(c, params, nullptr);
+}
+
+int rt_denoise_guided(rt_ctx* c, const rt_denoise_params* params, const rt_guide_params* guides) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    rt_guide_resolved g;
+    if (guide_resolve(guides, &g))
+        return set_err(c, RT_ERR_INVALID_ARG, "rt_denoise_guided: kn, kz, ka >= 0 and finite, reserved 0");
+    return run_denoise(c, params, &g);
 }
 
 int rt_read_denoised(rt_ctx* c, float* rgba) {

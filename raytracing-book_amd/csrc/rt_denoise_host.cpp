@@ -24,10 +24,30 @@ int denoise_resolve(const rt_denoise_params* p, rt_dn_resolved* out) {
     return RT_OK;
 }
 
+int guide_resolve(const rt_guide_params* p, rt_guide_resolved* out) {
+    out->kn = RT_GUIDE_DEFAULT_KN;
+    out->kz = RT_GUIDE_DEFAULT_KZ;
+    out->ka = RT_GUIDE_DEFAULT_KA;
+    if (!p) return RT_OK;
+    for (int r : p->reserved)
+        if (r != 0) return RT_ERR_INVALID_ARG;
+    const float k[3] = {p->kn, p->kz, p->ka};
+    for (float v : k)
+        if (!(v >= 0.0f) || !dn_finite(v)) return RT_ERR_INVALID_ARG;
+    out->kn = p->kn;
+    out->kz = p->kz;
+    out->ka = p->ka;
+    return RT_OK;
+}
+
 }  // namespace rt_impl
 
-extern "C" int rt_denoise_host(const float* image, const float* m2, const int32_t* tile_frames, int n_tiles, int width,
-                               int height, const rt_denoise_params* params, float* rgba_out) {
+namespace {
+
+// The filter over caller arrays; nd / ai NULL: unguided (rt_denoise_host).
+int denoise_host(const float* image, const float* m2, const int32_t* tile_frames, int n_tiles, const float* nd,
+                 const float* ai, int width, int height, const rt_denoise_params* params, const rt_guide_params* guides,
+                 float* rgba_out) {
     if (!image || !m2 || !tile_frames || !rgba_out) return RT_ERR_INVALID_ARG;
     if (width < 1 || height < 1 || width > RT_MAX_IMAGE_DIM || height > RT_MAX_IMAGE_DIM ||
         (size_t)width * height > ((size_t)1 << 30))
@@ -38,9 +58,19 @@ extern "C" int rt_denoise_host(const float* image, const float* m2, const int32_
         if (tile_frames[t] < 2) return RT_ERR_INVALID_ARG;
     rt_dn_resolved prm;
     if (rt_impl::denoise_resolve(params, &prm)) return RT_ERR_INVALID_ARG;
+    rt_guide_resolved gp = {0.0f, 0.0f, 0.0f};
+    if (nd && rt_impl::guide_resolve(guides, &gp)) return RT_ERR_INVALID_ARG;
+    const bool guided = nd && dn_guides_on(gp);
     const size_t n = (size_t)width * height;
     try {
-        std::vector<rt_dn4> a(n), b(n);
+        std::vector<rt_dn4> a(n), b(n), gnd, gai;
+        if (guided) {
+            gnd.resize(n);
+            gai.resize(n);
+            std::memcpy(gnd.data(), nd, n * sizeof(rt_dn4));
+            std::memcpy(gai.data(), ai, n * sizeof(rt_dn4));
+        }
+        const rt_dn_guides G = {gnd.data(), gai.data(), gp.kn, gp.kz, gp.ka};
         std::vector<float> vb(n);
         for (int y = 0; y < height; y++)
             for (int x = 0; x < width; x++) {
@@ -55,7 +85,9 @@ extern "C" int rt_denoise_host(const float* image, const float* m2, const int32_
                 for (int x = 0; x < width; x++) vb[(size_t)y * width + x] = dn_vb(src, width, height, x, y);
             for (int y = 0; y < height; y++)
                 for (int x = 0; x < width; x++)
-                    dst[(size_t)y * width + x] = dn_filter(src, vb.data(), width, height, x, y, 1 << lv, prm.k);
+                    dst[(size_t)y * width + x] =
+                        guided ? dn_filter_guided(src, vb.data(), width, height, x, y, 1 << lv, prm.k, G)
+                               : dn_filter(src, vb.data(), width, height, x, y, 1 << lv, prm.k);
             rt_dn4* t = src;
             src = dst;
             dst = t;
@@ -69,4 +101,19 @@ extern "C" int rt_denoise_host(const float* image, const float* m2, const int32_
         return RT_ERR_NOMEM;
     }
     return RT_OK;
+}
+
+}  // namespace
+
+extern "C" int rt_denoise_host(const float* image, const float* m2, const int32_t* tile_frames, int n_tiles, int width,
+                               int height, const rt_denoise_params* params, float* rgba_out) {
+    return denoise_host(image, m2, tile_frames, n_tiles, nullptr, nullptr, width, height, params, nullptr, rgba_out);
+}
+
+extern "C" int rt_denoise_guided_host(const float* image, const float* m2, const int32_t* tile_frames, int n_tiles,
+                                      const float* normal_depth, const float* albedo_id, int width, int height,
+                                      const rt_denoise_params* params, const rt_guide_params* guides, float* rgba_out) {
+    if (!normal_depth || !albedo_id) return RT_ERR_INVALID_ARG;
+    return denoise_host(image, m2, tile_frames, n_tiles, normal_depth, albedo_id, width, height, params, guides,
+                        rgba_out);
 }

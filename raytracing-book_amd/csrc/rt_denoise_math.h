@@ -59,19 +59,54 @@ RT_HD float dn_vb(const rt_dn4* __restrict__ src, int W, int H, int x, int y) {
     return acc / ws;
 }
 
+// The guides of rt_denoise_guided (rt.h): the first-hit buffers normal_depth = (N, t) and albedo_id =
+// (A, id bits), one float4 each per pixel, and the three strengths.  A pixel is guide-good when its
+// N, t and A are all finite; it is a miss when its id word is RT_FEATURE_MISS.
+struct rt_dn_guides {
+    const rt_dn4* nd;
+    const rt_dn4* ai;
+    float kn, kz, ka;
+};
+RT_HD int dn_guide_good(const rt_dn4 nd, const rt_dn4 ai) {
+    return dn_finite(nd.x) && dn_finite(nd.y) && dn_finite(nd.z) && dn_finite(nd.w) && dn_finite(ai.x) &&
+           dn_finite(ai.y) && dn_finite(ai.z);
+}
+RT_HD int dn_guide_hit(const rt_dn4 ai) { return rt_f2u(ai.w) != 0xFFFFFFFFu; }
+// The guide factor g of tap q of pixel p (rt.h): 1 when either is not guide-good, 0 across a hit / miss
+// boundary, else (gn * gz) * ga, a term whose k is exactly 0 being exactly 1 and gn, gz being 1 between
+// two misses.
+RT_HD float dn_guide_weight(const rt_dn4 ndp, const rt_dn4 aip, const rt_dn4 ndq, const rt_dn4 aiq, float kn, float kz,
+                            float ka) {
+    if (!(dn_guide_good(ndp, aip) && dn_guide_good(ndq, aiq))) return 1.0f;
+    const int hp = dn_guide_hit(aip), hq = dn_guide_hit(aiq);
+    if (hp != hq) return 0.0f;
+    float gn = 1.0f, gz = 1.0f, ga = 1.0f;
+    if (hp && kn != 0.0f) gn = g_max(0.0f, 1.0f - kn * (1.0f - ((ndp.x * ndq.x + ndp.y * ndq.y) + ndp.z * ndq.z)));
+    if (hp && kz != 0.0f) gz = g_max(0.0f, 1.0f - kz * (fabsf(ndp.w - ndq.w) / (g_max(ndp.w, ndq.w) + 1e-30f)));
+    if (ka != 0.0f)
+        ga = g_max(0.0f, 1.0f - ka * ((fabsf(aip.x - aiq.x) + fabsf(aip.y - aiq.y)) + fabsf(aip.z - aiq.z)));
+    return (gn * gz) * ga;
+}
+
 // One level at p with step s: taps (dy, dx) in {-2 .. 2}^2 row-major, q = p + s * (dx, dy), the
 // centre and taps outside the image or bad skipped (read at the clamped position, sums untouched):
 //   d  = fabsf(y(p) - y(q)) / (k * sqrtf(Vb(p) + Vb(q)) + 1e-30f)
-//   w  = (h[dy] * h[dx]) * g_max(0, 1 - d)
+//   w  = (h[dy] * h[dx]) * g_max(0, 1 - d)            (GUIDED: that times dn_guide_weight(p, q))
 //   sw = sw + w;  sc = sc + w * (C(q) - C(p)) per channel;  sv = sv + (w * w) * V(q)
 // then den = h0 + sw,  C' = C(p) + sc / den,  V' = ((h0 * h0) * V(p) + sv) / (den * den).
-// A bad p is returned as it is.
-RT_HD rt_dn4 dn_filter(const rt_dn4* __restrict__ src, const float* __restrict__ vb, int W, int H, int x, int y, int s,
-                       float k) {
+// A bad p is returned as it is.  GUIDED = false compiles to rt_denoise's filter as it was.
+template <bool GUIDED>
+RT_HD rt_dn4 dn_filter_t(const rt_dn4* __restrict__ src, const float* __restrict__ vb, int W, int H, int x, int y, int s,
+                         float k, const rt_dn_guides& G) {
     const size_t p = (size_t)y * W + x;
     const rt_dn4 cp = src[p];
     if (dn_bad(cp)) return cp;
     const float yp = dn_lum(cp), vbp = vb[p];
+    rt_dn4 ndp = cp, aip = cp;
+    if (GUIDED) {
+        ndp = G.nd[p];
+        aip = G.ai[p];
+    }
     float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sv = 0.0f;
 #pragma unroll
     for (int dy = -2; dy <= 2; dy++) {
@@ -85,7 +120,8 @@ RT_HD rt_dn4 dn_filter(const rt_dn4* __restrict__ src, const float* __restrict__
             const float vbq = vb[q];
             const bool use = in && !dn_bad(cq);
             const float d = fabsf(yp - dn_lum(cq)) / (k * sqrtf(vbp + vbq) + 1e-30f);
-            const float w = (dn_h5(dy) * dn_h5(dx)) * g_max(0.0f, 1.0f - d);
+            float w = (dn_h5(dy) * dn_h5(dx)) * g_max(0.0f, 1.0f - d);
+            if (GUIDED) w = w * dn_guide_weight(ndp, aip, G.nd[q], G.ai[q], G.kn, G.kz, G.ka);
             sw = use ? sw + w : sw;
             sr = use ? sr + w * (cq.x - cp.x) : sr;
             sg = use ? sg + w * (cq.y - cp.y) : sg;
@@ -101,6 +137,20 @@ RT_HD rt_dn4 dn_filter(const rt_dn4* __restrict__ src, const float* __restrict__
     o.w = ((RT_DN_H0 * RT_DN_H0) * cp.w + sv) / (den * den);
     return o;
 }
+RT_HD rt_dn4 dn_filter(const rt_dn4* __restrict__ src, const float* __restrict__ vb, int W, int H, int x, int y, int s,
+                       float k) {
+    const rt_dn_guides none = {nullptr, nullptr, 0.0f, 0.0f, 0.0f};
+    return dn_filter_t<false>(src, vb, W, H, x, y, s, k, none);
+}
+RT_HD rt_dn4 dn_filter_guided(const rt_dn4* __restrict__ src, const float* __restrict__ vb, int W, int H, int x, int y,
+                              int s, float k, const rt_dn_guides& G) {
+    return dn_filter_t<true>(src, vb, W, H, x, y, s, k, G);
+}
 
 // The filter's parameters after defaults and checks (rt_denoise_host.cpp rt_denoise_resolve).
 struct rt_dn_resolved { int levels; float k; };
+// The guide strengths after defaults and checks (rt_denoise_host.cpp guide_resolve).
+struct rt_guide_resolved { float kn, kz, ka; };
+// With all three strengths exactly 0 no guide applies at all (g = 1 on every tap, the hit / miss rule
+// included): the filter is rt_denoise's, bit for bit.
+RT_HD int dn_guides_on(const rt_guide_resolved g) { return g.kn != 0.0f || g.ka != 0.0f || g.kz != 0.0f; }

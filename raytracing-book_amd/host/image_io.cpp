@@ -61,6 +61,12 @@ int rts_save_png(const float* rgba, int width, int height, const char* path) {
     if (!rgba || !path || width <= 0 || height <= 0) return RT_ERR_INVALID_ARG;
     std::vector<uint8_t> rgb((size_t)width * height * 3);
     rts_tonemap_rgb8(rgba, width, height, rgb.data());
+    return rts_save_png_rgb8(rgb.data(), width, height, path);
+}
+
+int rts_save_png_rgb8(const uint8_t* rgb8, int width, int height, const char* path) {
+    if (!rgb8 || !path || width <= 0 || height <= 0) return RT_ERR_INVALID_ARG;
+    const std::vector<uint8_t> rgb(rgb8, rgb8 + (size_t)width * height * 3);
     std::vector<uint8_t> raw;
     raw.reserve((size_t)height * (1 + (size_t)width * 3));
     for (int y = 0; y < height; y++) {

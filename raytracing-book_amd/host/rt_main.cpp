@@ -64,7 +64,7 @@ struct Opt {
 };
 
 // commons-cli Options in Main.getOptions order (Main.java:43-70)
-enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_DENOISE, O_DENOISE_LEVELS, O_DENOISE_K, O_RAW_OUT, O_N };
+enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_DENOISE, O_DENOISE_LEVELS, O_DENOISE_K, O_RAW_OUT, O_DENOISE_GUIDES, O_DENOISE_KN, O_DENOISE_KZ, O_DENOISE_KA, O_FEATURES_OUT, O_N };
 const Opt kOpts[O_N] = {
     {"h", "help", false, "print help message"},
     {"s", "scene", true, "scene ID"},
@@ -85,6 +85,11 @@ const Opt kOpts[O_N] = {
     {nullptr, "denoise-levels", true, "with --denoise: filter levels, 1..5 (default 3)"},
     {nullptr, "denoise-k", true, "with --denoise: edge-stopping width in standard deviations (default 3)"},
     {nullptr, "raw-output", true, "with --denoise: also save the unfiltered image to this .png file"},
+    {nullptr, "denoise-guides", false, "with --denoise: guide the filter by first-hit normal, depth and albedo"},
+    {nullptr, "denoise-kn", true, "with --denoise-guides: strength of the normal term, >= 0"},
+    {nullptr, "denoise-kz", true, "with --denoise-guides: strength of the depth term, >= 0"},
+    {nullptr, "denoise-ka", true, "with --denoise-guides: strength of the albedo term, >= 0"},
+    {nullptr, "features-output", true, "save first-hit <arg>_normal.png, <arg>_albedo.png and <arg>_depth.png"},
 };
 
 // HelpFormatter.printHelp("OpenGL Ray Tracer", options): options sorted by key.
@@ -270,6 +275,31 @@ int main(int argc, char** argv) {
         if (devices.size() > 1) die("rtrender", "--denoise renders on one device (--devices names more)");
         if (spp < 2) die("rtrender", "--denoise needs -spp >= 2 (a variance takes two frames)");
     }
+    const bool guides = seen[O_DENOISE_GUIDES];
+    if (guides && !denoise) die("rtrender", "--denoise-guides goes with --denoise");
+    if (!guides && (seen[O_DENOISE_KN] || seen[O_DENOISE_KZ] || seen[O_DENOISE_KA]))
+        die("rtrender", "--denoise-kn, --denoise-kz and --denoise-ka go with --denoise-guides");
+    rt_guide_params guide_params;
+    std::memset(&guide_params, 0, sizeof(guide_params));
+    guide_params.kn = RT_GUIDE_DEFAULT_KN;
+    guide_params.kz = RT_GUIDE_DEFAULT_KZ;
+    guide_params.ka = RT_GUIDE_DEFAULT_KA;
+    {
+        const int which[3] = {O_DENOISE_KN, O_DENOISE_KZ, O_DENOISE_KA};
+        float* into[3] = {&guide_params.kn, &guide_params.kz, &guide_params.ka};
+        for (int i = 0; i < 3; i++) {
+            if (!seen[which[i]]) continue;
+            char* end = nullptr;
+            const float v = std::strtof(val[which[i]].c_str(), &end);
+            if (val[which[i]].empty() || *end != '\0' || !(v >= 0.0f) || !(v <= 3.0e38f))
+                die("rtrender", (std::string("--") + kOpts[which[i]].lng + " must be a finite number >= 0").c_str());
+            *into[i] = v;
+        }
+    }
+    const std::string features_output = get(O_FEATURES_OUT, nullptr);
+    if (seen[O_FEATURES_OUT] && features_output.empty()) die("rtrender", "--features-output needs a file prefix");
+    if (seen[O_FEATURES_OUT] && devices.size() > 1)
+        die("rtrender", "--features-output renders on one device (--devices names more)");
 
     rts_scene* scene = nullptr;
     if (rts_build(scene_id, width, height, (uint64_t)seed, nullptr, &scene) != 0) die("rts_build", rts_last_error());
@@ -303,9 +333,14 @@ int main(int argc, char** argv) {
     chk(rt_set_params(ctx, max_depth, info.background, sqrt_spp, recip), "rt_set_params");
     chk(rt_resize(ctx, width, height), "rt_resize");
     if (denoise) chk(rt_set_moments(ctx, 1), "rt_set_moments");
+    // the first-hit pass, once: the scene and the camera do not change from here on
+    if (guides || !features_output.empty()) chk(rt_render_features(ctx), "rt_render_features");
     // the image to save: through the filter with --denoise (once every tile holds two frames), else as rendered
     auto read_shown = [&](float* px, bool filtered) {
-        if (filtered) {
+        if (filtered && guides) {
+            chk(rt_denoise_guided(ctx, &dn_params, &guide_params), "rt_denoise_guided");
+            chk(rt_read_denoised(ctx, px), "rt_read_denoised");
+        } else if (filtered) {
             chk(rt_denoise(ctx, &dn_params), "rt_denoise");
             chk(rt_read_denoised(ctx, px), "rt_read_denoised");
         } else {
@@ -384,6 +419,9 @@ int main(int argc, char** argv) {
         std::vector<float> rgba((size_t)width * height * 4);
         read_shown(rgba.data(), denoise);
         if (denoise) std::printf("Denoise: levels %d, k %g\n", dn_params.levels, (double)dn_params.k);
+        if (guides)
+            std::printf("Denoise guides: kn %g, kz %g, ka %g\n", (double)guide_params.kn, (double)guide_params.kz,
+                        (double)guide_params.ka);
         if (rts_save_png(rgba.data(), width, height, output.c_str()) != 0)
             uncaught("java.lang.RuntimeException", "Failed to save texture as PNG");
         char abs_path[PATH_MAX];
@@ -398,6 +436,38 @@ int main(int argc, char** argv) {
         char abs_path[PATH_MAX];
         const char* shown = realpath(raw_output.c_str(), abs_path) ? abs_path : raw_output.c_str();
         std::printf("The unfiltered image has been saved to: %s\n", shown);
+    }
+    if (!features_output.empty()) {
+        // normal: N * 0.5 + 0.5; depth: t over the largest hit t, a miss black (both as bytes, no tonemap);
+        // albedo: through the image's tonemap
+        const size_t n = (size_t)width * height;
+        std::vector<float> nd(n * 4), ai(n * 4);
+        chk(rt_read_features(ctx, nd.data(), ai.data()), "rt_read_features");
+        float tmax = 0.0f;
+        for (size_t i = 0; i < n; i++)
+            if (nd[i * 4 + 3] > tmax && nd[i * 4 + 3] <= 3.0e38f) tmax = nd[i * 4 + 3];
+        auto byte_of = [](float v) { return (uint8_t)(v <= 0.0f ? 0 : v >= 1.0f ? 255 : (int)(v * 255.0f + 0.5f)); };
+        std::vector<uint8_t> nrm(n * 3), dep(n * 3);
+        for (size_t i = 0; i < n; i++) {
+            const float t = nd[i * 4 + 3];
+            const uint8_t z = (t > 0.0f && tmax > 0.0f && t <= tmax) ? byte_of(t / tmax) : 0;
+            for (int c = 0; c < 3; c++) {
+                nrm[i * 3 + c] = byte_of(nd[i * 4 + c] * 0.5f + 0.5f);
+                dep[i * 3 + c] = z;
+            }
+            ai[i * 4 + 3] = 1.0f;   // (the id's bits are not a colour)
+        }
+        const std::string names[3] = {features_output + "_normal.png", features_output + "_albedo.png",
+                                      features_output + "_depth.png"};
+        if (rts_save_png_rgb8(nrm.data(), width, height, names[0].c_str()) != 0 ||
+            rts_save_png(ai.data(), width, height, names[1].c_str()) != 0 ||
+            rts_save_png_rgb8(dep.data(), width, height, names[2].c_str()) != 0)
+            uncaught("java.lang.RuntimeException", "Failed to save texture as PNG");
+        for (const std::string& nm : names) {
+            char abs_path[PATH_MAX];
+            const char* shown = realpath(nm.c_str(), abs_path) ? abs_path : nm.c_str();
+            std::printf("A first-hit feature image has been saved to: %s\n", shown);
+        }
     }
     rt_destroy(ctx);
     rts_free(scene);

@@ -84,6 +84,13 @@ class RtDenoiseParams(ctypes.Structure):
     _fields_ = [("levels", ctypes.c_int), ("k", ctypes.c_float), ("reserved", ctypes.c_int * 6)]
 
 
+class RtGuideParams(ctypes.Structure):
+    """rt.h rt_guide_params."""
+    _fields_ = [("kn", ctypes.c_float), ("kz", ctypes.c_float), ("ka", ctypes.c_float), ("reserved", ctypes.c_int * 5)]
+
+
+RT_FEATURE_MISS = 0xFFFFFFFF   # rt.h
+
 RT_PK_N = 33   # rt_debug.h RT_PK_N
 
 
@@ -138,6 +145,13 @@ def _amd_protos(L, old_rev=False):
         _proto(L, "rt_denoise", i, vp, dp_p)
         _proto(L, "rt_read_denoised", i, vp, c_float_p)
         _proto(L, "rt_denoise_host", i, c_float_p, c_float_p, i32_p, i, i, i, dp_p, c_float_p)
+    if not old_rev or hasattr(L, "rt_render_features"):   # ... or from before the first-hit feature buffers
+        dp_p, gp_p, i32_p = ctypes.POINTER(RtDenoiseParams), ctypes.POINTER(RtGuideParams), ctypes.POINTER(ctypes.c_int32)
+        _proto(L, "rt_render_features", i, vp)
+        _proto(L, "rt_read_features", i, vp, c_float_p, c_float_p)
+        _proto(L, "rt_denoise_guided", i, vp, dp_p, gp_p)
+        _proto(L, "rt_denoise_guided_host", i, c_float_p, c_float_p, i32_p, i, c_float_p, c_float_p, i, i, dp_p, gp_p,
+               c_float_p)
     _proto(L, "rt_abi_version", i)
     _proto(L, "rt_create", i, i, c_int_p, ctypes.POINTER(vp))
     _proto(L, "rt_destroy", i, vp)

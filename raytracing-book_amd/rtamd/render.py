@@ -265,6 +265,51 @@ def denoise_host(image, m2, tile_frames, levels=None, k=None, lib=None):
     return out
 
 
+def _guide_params(guides):
+    """rt_guide_params for (kn, kz, ka); True = NULL (the library's defaults)."""
+    if guides is True:
+        return None
+    kn, kz, ka = guides
+    p = _lib.RtGuideParams()
+    p.kn, p.kz, p.ka = float(kn), float(kz), float(ka)
+    return ctypes.byref(p)
+
+
+def denoise_guided_host(image, m2, tile_frames, normal_depth, albedo_id, levels=None, k=None, guides=True, lib=None):
+    """rt_denoise_guided_host (host only): denoise_host with the first-hit guides.  normal_depth and
+    albedo_id are [H, W, 4] float32 (albedo_id's w holds the id's bits); guides is (kn, kz, ka), or True
+    for the library's defaults."""
+    L = lib or _lib.amd()
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    mom = np.ascontiguousarray(m2, dtype=np.float32)
+    nd = np.ascontiguousarray(normal_depth, dtype=np.float32)
+    ai = np.ascontiguousarray(albedo_id, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 4 or mom.shape != img.shape or nd.shape != img.shape or ai.shape != img.shape:
+        raise ValueError("image, m2, normal_depth and albedo_id are [H, W, 4]")
+    H, W = img.shape[:2]
+    nt = ((W + 7) // 8) * ((H + 7) // 8)
+    tf = np.ascontiguousarray(tile_frames, dtype=np.int32).ravel()
+    if tf.size == 1:
+        tf = np.full(nt, tf[0], np.int32)
+    out = np.empty_like(img)
+    rc = L.rt_denoise_guided_host(img.ctypes.data_as(c_float_p), mom.ctypes.data_as(c_float_p),
+                                  tf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(tf.size),
+                                  nd.ctypes.data_as(c_float_p), ai.ctypes.data_as(c_float_p), W, H,
+                                  _denoise_params(levels, k), _guide_params(guides), out.ctypes.data_as(c_float_p))
+    if rc != 0:
+        raise RTError(rc, "rt_denoise_guided_host: levels 1..5, k > 0, kn, kz, ka >= 0, one count >= 2 per 8x8 tile required")
+    return out
+
+
+def pack_albedo_id(albedo, ids):
+    """(albedo [H, W, 3] float32, id [H, W] uint32) -> albedo_id [H, W, 4] float32, the id's bits in w."""
+    a = np.ascontiguousarray(albedo, dtype=np.float32)
+    out = np.empty(a.shape[:2] + (4,), np.float32)
+    out[..., :3] = a
+    out.view(np.uint32)[..., 3] = np.ascontiguousarray(ids, dtype=np.uint32)
+    return out
+
+
 SHAPES = {0: "fast-lds", 1: "fast-global", 2: "link-lds", 3: "meta-lds", 4: "meta-global", 5: "link-two-level"}
 
 
@@ -508,13 +553,36 @@ class RenderContext:
         return done.value, s.as_dict()
 
     # -- the variance-guided preview filter (rt.h rt_denoise)
-    def denoise(self, levels=None, k=None):
+    def denoise(self, levels=None, k=None, guides=None):
         """rt_denoise + rt_read_denoised: the filtered image as [H, W, 4] float32 (w = 1).  Image and
-        moments are left as they are.  Needs set_moments() and at least two frames in every tile."""
-        self._check(self._L.rt_denoise(self._h, _denoise_params(levels, k)))
+        moments are left as they are.  Needs set_moments() and at least two frames in every tile.
+        guides: None = unguided; (kn, kz, ka), or True for the library's defaults = rt_denoise_guided
+        over the first-hit buffers (render_features() first)."""
+        if guides is None or guides is False:
+            self._check(self._L.rt_denoise(self._h, _denoise_params(levels, k)))
+        else:
+            self._check(self._L.rt_denoise_guided(self._h, _denoise_params(levels, k), _guide_params(guides)))
         out = np.empty((self.local_rows, self.width, 4), dtype=np.float32)
         self._check(self._L.rt_read_denoised(self._h, out.ctypes.data_as(c_float_p)))
         return out
+
+    # -- the first-hit feature buffers (rt.h rt_render_features)
+    def render_features(self):
+        """rt_render_features: queue the first-hit pass (one centre ray per pixel, media left out)."""
+        self._check(self._L.rt_render_features(self._h))
+
+    def read_features_raw(self):
+        """rt_read_features as stored: (normal_depth, albedo_id), [H, W, 4] float32 each."""
+        nd = np.empty((self.local_rows, self.width, 4), dtype=np.float32)
+        ai = np.empty_like(nd)
+        self._check(self._L.rt_read_features(self._h, nd.ctypes.data_as(c_float_p), ai.ctypes.data_as(c_float_p)))
+        return nd, ai
+
+    def read_features(self):
+        """rt_read_features: (normal_depth [H, W, 4] f32, albedo [H, W, 3] f32, id [H, W] u32); a miss has
+        N = 0, t = -1, the background colour and id RT_FEATURE_MISS."""
+        nd, ai = self.read_features_raw()
+        return nd, np.ascontiguousarray(ai[..., :3]), np.ascontiguousarray(ai.view(np.uint32)[..., 3])
 
     def read_samples(self):
         """rt_debug_read_samples: the last launch's staged colours, [n_frames, local_rows, W, 4]."""
