@@ -59,6 +59,57 @@ enum {
 int rt_debug_eval_op(int device, int op, int form, const void* recs, size_t rec_bytes, const float* rows, int n,
                      int tex_format, int tex_w, int tex_h, const void* tex, unsigned int* out, int flags[4]);
 
+/* Evaluate one of the render kernels' sampling, light, camera or shading operations on the first
+ * device of `ctx`, one lane per row, by the device function the kernels call (csrc/rt_shade_eval.hip;
+ * tests/test_gpu_shade_ops.py compares every form with the CPU oracle's oracle_eval_shade_op word for
+ * word).  Rows run in whole waves in input order, padded with copies of the last row, as in
+ * rt_debug_eval_op.  The scene is the one the context uploaded: spheres, quads, boxes, dquads, media,
+ * lights, textures, camera, background and sqrt_spp.  The argument block comes from the functions
+ * rt_render uses (csrc/rt_args.h scene_args) with every LDS offset set to -1, so all records are read
+ * from global memory.
+ * Row i of `rows`: RT_SOP_ROW_F floats (ints as their bits):
+ *   [0..2] o   [3..5] d   [6] hit t   [7] tif (prim type | box face << 4 | prim index << 16)
+ *   [8] time   [9] px   [10] py   [11] rf   [12..14] acc   [15] UvSrc kind_idx   [16..18] UvSrc a, b, c
+ *   [19] frame_count
+ * Row i of `out`: RT_SOP_OUT_W 32-bit words (floats as their bits; unused words 0).
+ *   op                     device function     in                                  out words
+ *   RT_SOP_RAND            rnd                 px, py, rf                          6 successive draws, rf after
+ *   RT_SOP_ONB             transform_onb       vec = [0..2], normal = [3..5]       x, y, z
+ *   RT_SOP_UNIT_VEC        rand_unit_vec       px, py, rf                          x, y, z, rf after
+ *   RT_SOP_MEDIUM_TAIL     medium_tail         [0] neg_inv_density, [1] t1, [2] t2, hit, t (0 on a miss), rf after
+ *                                              [3] a = dot(d, d), [4] tmin,
+ *                                              [5] tmax, px, py, rf
+ *   RT_SOP_LIGHT_PDF       lights_pdf_value    o, d, time                          pdf
+ *   RT_SOP_LIGHT_DIR       lights_random       o, px, py, rf                       x, y, z, rf after
+ *   RT_SOP_CAMERA_RAY      start_path (base as px, py, frame_count, rf (= rf0)     time, o, d, rf after
+ *                          the render kernel
+ *                          writes it)
+ *   RT_SOP_SHADE           shade<>             o, d, t, tif, time, px, py, rf,     ended; result r, g, b when ended,
+ *                                              acc, UvSrc                          else o, d, acc (words 1..9);
+ *                                                                                  word 10 rf after
+ * form: 0, except RT_SOP_SHADE: 0 shade<false, false, false, false>, 1 shade<false, false, false, true>
+ * (the per-pass trims of the compact-box kernels: the no-light mixture).  Form 1 gives form 0's words
+ * but one: on a scene without lights, a row whose mixture draw is below 0.5 leaves rf one draw short of
+ * form 0's (word 10 is one float32 addition of 0.001 less), because the trim leaves out lights_random,
+ * whose draw nothing reads: such a row's path has ended, or goes on along vec3(0) and draws no more.
+ * The call runs validate() and scene_args() on the context, as rt_render does, so it may refresh the
+ * context's planned state (the walk's links, the scene extent, the leaf census); it renders nothing.
+ * The guard below checks the rows, not the scene: a hit's texture id is used as the scene holds it.
+ * Input guard: the rejection loops of rand_unit_vec and start_path never end on draws that are NaN, so
+ * unless every row's px and py are finite and in [0, 16384) and its rf is finite and in [0, 4096) the
+ * call returns RT_ERR_INVALID_ARG before anything is launched; likewise for a RT_SOP_SHADE row whose
+ * tif or UvSrc names a record the scene does not hold.  Other fields may be NaN or infinite.
+ * device < 0: the guard alone (ctx may be NULL), nothing is launched and out is not written. */
+enum {
+    RT_SOP_RAND = 0, RT_SOP_ONB, RT_SOP_UNIT_VEC, RT_SOP_MEDIUM_TAIL, RT_SOP_LIGHT_PDF, RT_SOP_LIGHT_DIR,
+    RT_SOP_CAMERA_RAY, RT_SOP_SHADE, RT_SOP_N
+};
+#define RT_SOP_ROW_F 20
+#define RT_SOP_OUT_W 12
+struct rt_ctx;
+int rt_debug_eval_shade_op(struct rt_ctx* ctx, int device, int op, int form, const float* rows, int n,
+                           unsigned int* out);
+
 /* Host-only: the threaded-BVH re-layout rt_upload_buffer(RT_BIND_BVH) builds
  * (32-byte rt_dnode records); out may be NULL to query the count. */
 int rt_debug_threaded_bvh(const void* nodes, size_t nbytes, void* out, size_t out_cap, int* n_out);

@@ -76,6 +76,8 @@ def lib():
         L.oracle_checker_parity.argtypes = [ctypes.c_float] * 4
         L.oracle_eval_op.argtypes = [ctypes.c_int, ctypes.c_void_p, fp, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                      ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint32)]
+        L.oracle_eval_shade_op.argtypes = [ctypes.POINTER(OracleSceneDesc), ctypes.c_int, fp, ctypes.c_int,
+                                           ctypes.POINTER(ctypes.c_uint32)]
         _L = L
     return _L
 
@@ -266,6 +268,45 @@ def checker_rows(p, which=0):
 def checker_parities(scales, p, which=0):
     """checkerboard()'s parity (0 even, 1 odd) of p [n, 3] under scale scales[which]."""
     return _f(eval_op("texture", checker_rows(p, which), tex=checker_table(scales))[:, 0]) != 0.0
+
+
+# ---- the sampling, light, camera and shading operations on a scene (rt_debug.h's rt_debug_eval_shade_op
+# layout: RT_SOP_* numbers, rows of 20 floats, 12 output words)
+SHADE_OPS = {"rand": 0, "onb": 1, "unit_vec": 2, "medium_tail": 3, "light_pdf": 4, "light_dir": 5, "camera_ray": 6,
+             "shade": 7}
+SOP_ROW_F, SOP_OUT_W = 20, 12
+# float index of each row field (ints as their bits)
+SOP_O, SOP_D, SOP_T, SOP_TIF, SOP_TIME, SOP_PX, SOP_PY, SOP_RF, SOP_ACC, SOP_UVK, SOP_UV, SOP_FRAME = \
+    0, 3, 6, 7, 8, 9, 10, 11, 12, 15, 16, 19
+
+
+def shade_rows(n, o=None, d=None, t=0.0, tif=0, time=0.0, px=0.0, py=0.0, rf=0.0, acc=1.0, uvk=0, uv=None, frame=1):
+    """[n, 20] float32 rows of rt_debug_eval_shade_op (each argument a scalar or an array over the rows)."""
+    rows = np.zeros((n, SOP_ROW_F), np.float32)
+    iv = rows.view(np.int32)
+    if o is not None:
+        rows[:, 0:3] = np.asarray(o, np.float32).reshape(-1, 3)
+    if d is not None:
+        rows[:, 3:6] = np.asarray(d, np.float32).reshape(-1, 3)
+    rows[:, SOP_T], rows[:, SOP_TIME], rows[:, SOP_PX], rows[:, SOP_PY], rows[:, SOP_RF] = t, time, px, py, rf
+    rows[:, 12:15] = np.asarray(acc, np.float32).reshape(-1, 3) if np.ndim(acc) else acc
+    iv[:, SOP_TIF], iv[:, SOP_UVK], iv[:, SOP_FRAME] = tif, uvk, frame
+    if uv is not None:
+        rows[:, 16:19] = np.asarray(uv, np.float32).reshape(-1, 3)
+    return rows
+
+
+def eval_shade_op(oscene, op, rows):
+    """The oracle's result words [n, 12] uint32 of `op` (a name of SHADE_OPS) over rows on an OracleScene."""
+    rows = np.ascontiguousarray(rows, np.float32)
+    n = rows.shape[0]
+    assert rows.shape == (n, SOP_ROW_F)
+    out = np.zeros((n, SOP_OUT_W), np.uint32)
+    rc = lib().oracle_eval_shade_op(ctypes.byref(oscene.desc), SHADE_OPS[op], _fp(rows), n,
+                                    out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    if rc != 0:
+        raise ValueError(f"oracle_eval_shade_op({op}) failed ({rc})")
+    return out
 
 
 BUILTINS = {"sin": 0, "cos": 1, "log": 2, "acos": 3, "atan2": 4, "fract": 5, "sqrt": 6, "inversesqrt": 7}

@@ -437,18 +437,24 @@ bool medium_boundary_hits(Inv& I, const Ray& ray, const rt_medium& medium, HitRe
     return true;
 }
 
+// :172-187 -- after the two boundary hits: the clamps to ray_t, the early-out, then the one rand().
+// ray_length = length(ray.dir) (:180: a pure value, taken by the caller).
+bool medium_tail(Inv& I, float neg_inv_density, float t1, float t2, float ray_length, Interval ray_t, float& t) {
+    if (t1 < ray_t.min) t1 = ray_t.min;
+    if (t2 > ray_t.max) t2 = ray_t.max;
+    if (t1 >= t2) return false;
+    if (t1 < 0.0f) t1 = 0.0f;
+    float distance_inside_boundary = (t2 - t1) * ray_length;
+    float hit_distance = neg_inv_density * g_log(rand(I));
+    if (hit_distance > distance_inside_boundary) return false;
+    t = t1 + hit_distance / ray_length;
+    return true;
+}
+
 bool hit_constant_medium(Inv& I, const Ray& ray, Interval ray_t, const rt_medium& medium, HitRecord& rec) {   // :162-193
     HitRecord rec1, rec2;
     if (!medium_boundary_hits(I, ray, medium, rec1, rec2)) return false;
-    if (rec1.t < ray_t.min) rec1.t = ray_t.min;
-    if (rec2.t > ray_t.max) rec2.t = ray_t.max;
-    if (rec1.t >= rec2.t) return false;
-    if (rec1.t < 0.0f) rec1.t = 0.0f;
-    float ray_length = g_length(ray.dir);
-    float distance_inside_boundary = (rec2.t - rec1.t) * ray_length;
-    float hit_distance = medium.neg_inv_density * g_log(rand(I));
-    if (hit_distance > distance_inside_boundary) return false;
-    rec.t = rec1.t + hit_distance / ray_length;
+    if (!medium_tail(I, medium.neg_inv_density, rec1.t, rec2.t, g_length(ray.dir), ray_t, rec.t)) return false;
     rec.p = add3(ray.o, scale3(ray.dir, rec.t));
     rec.normal = mk3(1.0f, 0.0f, 0.0f);
     rec.is_front_face = true;
@@ -731,26 +737,19 @@ Ray get_ray(Inv& I) {   // :268-296
     return ray;
 }
 
-v3 ray_color(Inv& I, Ray ray) {   // :298-343
-    const Scene& S = *I.S;
-    v3 final_color = mk3s(0.0f);
-    v3 acc = mk3s(1.0f);
-    HitRecord rec;
-    for (int i = 0; i < S.max_depth; i++) {
-        if (I.C) I.C->c.bounces++;
-        if (!trace_through_bvh(I, ray, Interval{0.001f, RT_INFINITY}, rec)) {
-            final_color = mul3(acc, S.background);
-            break;
-        }
+// The loop body of ray_color after a trace_through_bvh that hit (:310-339), on the material globals the
+// walk left (set_material_properties).  Returns true when the path ended, with its colour in final_color.
+bool shade_step(Inv& I, Ray& ray, const HitRecord& rec, v3& acc, v3& final_color) {
+    {
         bool skip_pdf = false;
         if (!scatter(I, ray, rec.p, rec.normal, rec.is_front_face, I.material, skip_pdf)) {
             final_color = mul3(acc, I.color_from_emission);
-            break;
+            return true;
         }
         ray.o = rec.p;
         if (skip_pdf) {
             acc = mul3(acc, I.attenuation);
-            continue;
+            return false;
         }
 #if defined(RT_PROBE_Q1)
         // probe builds only (tools/scene8_residual_probe.py): other readings of SURVEY App. A Q1 (no
@@ -769,10 +768,26 @@ v3 ray_color(Inv& I, Ray ray) {   // :298-343
         float pdf_value = 0.5f * lpdf + 0.5f * material_pdf_value(ray.dir, I.material, rec.normal);
         if (pdf_value == 0.0f) {
             final_color = mul3(acc, I.color_from_emission);
-            break;
+            return true;
         }
         float sp = scattering_pdf(rec.normal, ray.dir, I.material);
         acc = mul3(acc, divs3(scale3(I.attenuation, sp), pdf_value));
+    }
+    return false;
+}
+
+v3 ray_color(Inv& I, Ray ray) {   // :298-343
+    const Scene& S = *I.S;
+    v3 final_color = mk3s(0.0f);
+    v3 acc = mk3s(1.0f);
+    HitRecord rec;
+    for (int i = 0; i < S.max_depth; i++) {
+        if (I.C) I.C->c.bounces++;
+        if (!trace_through_bvh(I, ray, Interval{0.001f, RT_INFINITY}, rec)) {
+            final_color = mul3(acc, S.background);
+            break;
+        }
+        if (shade_step(I, ray, rec, acc, final_color)) break;
     }
     return final_color;
 }
@@ -1077,6 +1092,94 @@ int oracle_eval_op(int op, const void* recs, const float* rows, int n, int tex_f
                 v2 uvv = {d[0], d[1]};
                 v3 c = texture_color(I, ld3(o), word, uvv);
                 w[0] = rt_f2u(c.x); w[1] = rt_f2u(c.y); w[2] = rt_f2u(c.z);
+                break;
+            }
+            default: return -1;
+        }
+    }
+    return 0;
+}
+
+// The sampling, light, camera and shading operations over n rows in rt_debug_eval_shade_op's layout
+// (include/rt/rt_debug.h: its op numbers, rows of 20 floats, 12 output words per row) on scene d.
+int oracle_eval_shade_op(const oracle_scene_desc* d, int op, const float* rows, int n, uint32_t* out) {
+    Scene S;
+    if (!d || !make_scene(d, S)) return -1;
+    auto put3 = [](uint32_t* w, v3 v) { w[0] = rt_f2u(v.x); w[1] = rt_f2u(v.y); w[2] = rt_f2u(v.z); };
+    for (int i = 0; i < n; i++) {
+        const float* r = rows + (size_t)i * 20;
+        uint32_t* w = out + (size_t)i * 12;
+        for (int k = 0; k < 12; k++) w[k] = 0;
+        Inv I;
+        I.S = &S; I.C = nullptr;
+        I.pixel_coord = {r[9], r[10]};
+        I.rand_factor = r[11];
+        I.time = r[8];
+        I.attenuation = mk3s(0.0f); I.color_from_emission = mk3s(0.0f); I.material = 0;
+        std::memcpy(&I.frame_count, r + 19, 4);
+        const v3 o = ld3(r), dd = ld3(r + 3);
+        switch (op) {
+            case 0:   // rand
+                for (int k = 0; k < 6; k++) w[k] = rt_f2u(rand(I));
+                w[6] = rt_f2u(I.rand_factor);
+                break;
+            case 1: put3(w, transform_onb(o, dd)); break;
+            case 2: put3(w, rand_unit_vec(I)); w[3] = rt_f2u(I.rand_factor); break;
+            case 3: {   // medium_tail: length(ray.dir) = sqrt(a)
+                float t = 0.0f;
+                const bool hit = medium_tail(I, r[0], r[1], r[2], sqrtf(r[3]), Interval{r[4], r[5]}, t);
+                w[0] = hit; w[1] = rt_f2u(hit ? t : 0.0f); w[2] = rt_f2u(I.rand_factor);
+                break;
+            }
+            case 4: w[0] = rt_f2u(lights_pdf_value(I, o, dd)); break;
+            case 5: put3(w, lights_random(I, o)); w[3] = rt_f2u(I.rand_factor); break;
+            case 6: {   // main()'s time = rand(), then get_ray()
+                I.time = rand(I);
+                const Ray ray = get_ray(I);
+                w[0] = rt_f2u(I.time); put3(w + 1, ray.o); put3(w + 4, ray.dir); w[7] = rt_f2u(I.rand_factor);
+                break;
+            }
+            case 7: {
+                // the hit record and material globals the walk would have left for this closest hit
+                // (hitting.glsl:38-46, 122-131, 188-190; compute.glsl:197-224), the uv being the one the
+                // row carries (kind 1: get_sphere_uv of that sphere's hit point, kind 2: a quad's alpha, beta)
+                int32_t tif, uvk;
+                std::memcpy(&tif, r + 7, 4);
+                std::memcpy(&uvk, r + 15, 4);
+                const int type = tif & 0xF, face = (tif >> 4) & 0x7, idx = (int)((uint32_t)tif >> 16);
+                Ray ray{o, dd};
+                HitRecord rec;
+                rec.t = r[6];
+                rec.p = add3(ray.o, scale3(ray.dir, rec.t));
+                if ((uvk >> 16) == 2) rec.uv = {r[16], r[17]};
+                else if ((uvk >> 16) == 1) {
+                    if ((uvk & 0xFFFF) >= S.n_spheres) return -1;
+                    const rt_sphere& us = S.spheres[uvk & 0xFFFF];
+                    rec.uv = get_sphere_uv(sub3(ld3(r + 16), sphere_center(I, ld3(us.center1), ld3(us.center_vec))));
+                }
+                if (type == RT_MODEL_SPHERE && idx < S.n_spheres) {
+                    const rt_sphere& sp = S.spheres[idx];
+                    v3 outward = divs3(sub3(rec.p, sphere_center(I, ld3(sp.center1), ld3(sp.center_vec))), sp.radius);
+                    rec.is_front_face = is_front_face(ray.dir, outward);
+                    rec.normal = get_face_normal(outward, rec.is_front_face);
+                } else if ((type == RT_MODEL_QUAD && idx < S.n_quads && face == 0) ||
+                           (type == RT_MODEL_BOX && idx < S.n_boxes && face < 6)) {
+                    const rt_quad& q = type == RT_MODEL_QUAD ? S.quads[idx] : S.boxes[idx].quads[face];
+                    rec.is_front_face = is_front_face(ray.dir, ld3(q.normal));
+                    rec.normal = get_face_normal(ld3(q.normal), rec.is_front_face);
+                } else if (type == RT_MODEL_CONSTANT_MEDIUM && idx < S.n_media) {
+                    rec.normal = mk3(1.0f, 0.0f, 0.0f);
+                    rec.is_front_face = true;
+                } else {
+                    return -1;
+                }
+                set_material_properties(I, idx, type, rec.p, rec.uv, rec.is_front_face);
+                v3 acc = ld3(r + 12), fin = mk3s(0.0f);
+                const bool ended = shade_step(I, ray, rec, acc, fin);
+                w[0] = ended;
+                if (ended) put3(w + 1, fin);
+                else { put3(w + 1, ray.o); put3(w + 4, ray.dir); put3(w + 7, acc); }
+                w[10] = rt_f2u(I.rand_factor);
                 break;
             }
             default: return -1;

@@ -14,7 +14,10 @@
  * layout comments of RaytraceModel.java:139-219 vs compute.glsl structs, and
  * (c) statistical agreement with the reference gallery render of scene 6, and
  * (d) per operation (the oracle_eval_op entry points below) a float64 restatement of the shader
- * text within derived rounding bounds (tests/ref64.py, tests/test_ops_ref64.py);
+ * text within derived rounding bounds (tests/ref64.py, tests/test_ops_ref64.py), and (e) likewise the
+ * operations that choose a path's next direction and weight (oracle_eval_shade_op: rand as a float32
+ * composition, transform_onb, rand_unit_vec, the medium's tail, light pdf and direction, the camera ray and
+ * the shading step; tests/ref64_shade.py, tests/test_shade_ref64.py), draw counts included;
  * everything else is "parity unpinned" against the reference itself.
  */
 #ifndef RT_ORACLE_H
@@ -103,6 +106,14 @@ int oracle_checker_parity(float scale, float px, float py, float pz);
  * texture_color on slot 0).  Returns 0, or -1 for an unknown op or a Perlin table of another shape. */
 int oracle_eval_op(int op, const void* recs, const float* rows, int n, int tex_format, int tex_w, int tex_h,
                    const void* tex, uint32_t* out);
+/* The operations that decide where a path goes next and what it carries, over n rows in
+ * rt_debug_eval_shade_op's layout (include/rt/rt_debug.h: its op numbers RT_SOP_*, rows of 20 floats, 12
+ * output words per row) on scene d: rand, transform_onb, rand_unit_vec, the tail of hit_constant_medium
+ * after its two boundary hits (medium_tail), lights_pdf_value, lights_random, main()'s time = rand() with
+ * get_ray(), and the body of ray_color's loop after a trace that hit (shade_step, on the hit record and
+ * material globals that hit leaves).  ray_color and hit_constant_medium call the same medium_tail and
+ * shade_step.  Returns 0, or -1 for an unknown op or a shade row that names no record of the scene. */
+int oracle_eval_shade_op(const oracle_scene_desc* d, int op, const float* rows, int n, uint32_t* out);
 
 #ifdef __cplusplus
 }

@@ -142,6 +142,77 @@ int rt_debug_eval_op(int device, int op, int form, const void* recs, size_t rec_
     return rc;
 }
 
+// The host half checks the rows (the rejection loops never end on NaN draws; a shade row must name
+// records the scene holds), assembles the scene's argument block as rt_render does (scene_args) with
+// every LDS offset at -1, and binds the first device's copies; the device half is rt_shade_eval.hip.
+int rt_debug_eval_shade_op(rt_ctx* c, int device, int op, int form, const float* rows, int n, unsigned int* out) {
+    if (op < 0 || op >= RT_SOP_N || form < 0 || form > (op == RT_SOP_SHADE ? 1 : 0) || !rows || n < 0)
+        return RT_ERR_INVALID_ARG;
+    for (int i = 0; i < n; i++) {
+        const float* r = rows + (size_t)i * RT_SOP_ROW_F;
+        if (!(r[9] >= 0.0f && r[9] < 16384.0f) || !(r[10] >= 0.0f && r[10] < 16384.0f) ||
+            !(r[11] >= 0.0f && r[11] < 4096.0f))
+            return RT_ERR_INVALID_ARG;
+    }
+    if (device < 0) return RT_OK;
+    if (!c || !out) return RT_ERR_INVALID_ARG;
+    if (c->devs.empty()) return set_err(c, RT_ERR_STATE, "rt_debug_eval_shade_op: the context has no device");
+    if (!c->have_cam) return set_err(c, RT_ERR_STATE, "rt_set_camera before rt_debug_eval_shade_op");
+    if (!c->uploaded[RT_BIND_BVH]) return set_err(c, RT_ERR_STATE, "no BVH uploaded");
+    int r = validate(c);
+    if (r) return r;
+    if (op == RT_SOP_SHADE) {
+        const size_t count[4] = {c->n_records(RT_BIND_SPHERES), c->n_records(RT_BIND_QUADS),
+                                 c->n_records(RT_BIND_MEDIA), c->n_records(RT_BIND_BOXES)};
+        for (int i = 0; i < n; i++) {
+            int32_t tif, uvk;
+            std::memcpy(&tif, rows + (size_t)i * RT_SOP_ROW_F + 7, 4);
+            std::memcpy(&uvk, rows + (size_t)i * RT_SOP_ROW_F + 15, 4);
+            const int type = tif & 0xF, face = (tif >> 4) & 0x7;
+            const size_t idx = (uint32_t)tif >> 16;
+            const int which = type == RT_MODEL_SPHERE ? 0 : type == RT_MODEL_QUAD ? 1
+                            : type == RT_MODEL_CONSTANT_MEDIUM ? 2 : type == RT_MODEL_BOX ? 3 : -1;
+            if (which < 0 || idx >= count[which] || face > (type == RT_MODEL_BOX ? 5 : 0))
+                return set_err(c, RT_ERR_INVALID_ARG, "rt_debug_eval_shade_op: a row's tif names no record of the scene");
+            if ((uvk >> 16) == 1 && (size_t)(uvk & 0xFFFF) >= count[0])
+                return set_err(c, RT_ERR_INVALID_ARG, "rt_debug_eval_shade_op: a row's UvSrc names no sphere of the scene");
+        }
+    }
+    if (n == 0) return RT_OK;
+    rt_kernel_args a;
+    if ((r = scene_args(*c, a, &c->err))) return r;
+    a.perlin_lds = a.media_lds = a.sph_lds = a.sph_mat_lds = a.box_mat_lds = a.tex_lds = a.box_cmp_lds = a.leaf_lds = -1;
+    for (int& o : a.tex_lds_off) o = -1;
+    Device& d = c->devs[0];
+    HIPCHK(c, hipSetDevice(d.id));
+    HIPCHK(c, hipStreamSynchronize(d.stream));
+    a.spheres = (const rt_sphere*)d.spheres.ptr;
+    a.quads = (const rt_quad*)d.quads.ptr;
+    a.boxes = (const rt_box*)d.boxes.ptr;
+    a.dquads = (const float4*)d.dquads.ptr;
+    a.media = (const rt_medium*)d.media.ptr;
+    a.lights = (const int32_t*)d.lights.ptr;
+    for (int t = 0; t < 8; t++) a.tex[t].data = d.tex[t].ptr;
+    const int npad = (n + 63) / 64 * 64;
+    const size_t row_b = RT_SOP_ROW_F * sizeof(float), out_b = (size_t)npad * RT_SOP_OUT_W * 4;
+    std::vector<float> padded((size_t)npad * RT_SOP_ROW_F);   // rows 0..n-1, then the last row again
+    for (int i = 0; i < npad; i++) std::memcpy(&padded[(size_t)i * RT_SOP_ROW_F], rows + (size_t)std::min(i, n - 1) * RT_SOP_ROW_F, row_b);
+    void *d_rows = nullptr, *d_out = nullptr, *d_args = nullptr;
+    int rc = RT_OK;
+    if (hipMalloc(&d_rows, row_b * (size_t)npad) != hipSuccess || hipMalloc(&d_out, out_b) != hipSuccess ||
+        hipMalloc(&d_args, sizeof(a)) != hipSuccess)
+        rc = RT_ERR_DEVICE;
+    if (!rc && hipMemcpy(d_rows, padded.data(), row_b * (size_t)npad, hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_DEVICE;
+    if (!rc && hipMemset(d_out, 0, out_b) != hipSuccess) rc = RT_ERR_DEVICE;
+    if (!rc && hipMemcpy(d_args, &a, sizeof(a), hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_DEVICE;
+    if (!rc && rt_launch_eval_shade_op((const rt_kernel_args*)d_args, op, form, (const float*)d_rows, d_out, npad, nullptr))
+        rc = RT_ERR_DEVICE;
+    if (!rc && hipMemcpy(out, d_out, (size_t)n * RT_SOP_OUT_W * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = RT_ERR_DEVICE;
+    for (void* p : {d_rows, d_out, d_args})
+        if (p) (void)hipFree(p);
+    return rc ? set_err(c, rc, "rt_debug_eval_shade_op: a HIP call failed") : RT_OK;
+}
+
 int rt_debug_read_samples(rt_ctx* c, float* out, size_t cap_floats, int* n_frames) {
     if (!c || !n_frames) return RT_ERR_INVALID_ARG;
     if (!c->launched || c->staged_frames <= 0) return set_err(c, RT_ERR_STATE, "the last launch was not staged");

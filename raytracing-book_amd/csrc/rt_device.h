@@ -264,3 +264,7 @@ int rt_launch_eval_builtin(int fn, const float* dx, const float* dy, float* dout
 // debug: evaluate the kernels' own operations (rt_debug.h rt_debug_eval_op; rt_ops_eval.hip); n a multiple of 64
 int rt_launch_eval_op(const rt_kernel_args* dargs, int op, int form, const void* drecs, const float* drows, void* dout,
                       int n, void* stream);
+// debug: evaluate the kernels' sampling, light, camera and shading operations on a context's scene
+// (rt_debug.h rt_debug_eval_shade_op; rt_shade_eval.hip); n a multiple of 64
+int rt_launch_eval_shade_op(const rt_kernel_args* dargs, int op, int form, const float* drows, void* dout, int n,
+                            void* stream);

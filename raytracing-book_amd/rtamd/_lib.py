@@ -214,6 +214,8 @@ def _amd_protos(L, old_rev=False):
     if not old_rev or hasattr(L, "rt_debug_eval_op"):   # ... or from before the per-operation evaluator
         _proto(L, "rt_debug_eval_op", i, i, i, i, vp, sz, c_float_p, i, i, i, i, vp, ctypes.POINTER(ctypes.c_uint32),
                c_int_p)
+    if not old_rev or hasattr(L, "rt_debug_eval_shade_op"):   # ... or from before the shading-operation evaluator
+        _proto(L, "rt_debug_eval_shade_op", i, vp, i, i, i, c_float_p, i, ctypes.POINTER(ctypes.c_uint32))
     _proto(L, "rt_set_bvh_mode", i, vp, i)
     _proto(L, "rt_debug_walk_bvh", i, vp, vp, sz, ctypes.POINTER(sz))
     _proto(L, "rt_debug_build_sah_bvh", i, vp, sz, vp, sz, vp, sz, vp, sz, vp, sz, i, c_float_p, f, vp, sz,
@@ -334,3 +336,23 @@ def debug_eval_op(op, form, rows, recs=None, tex=None, device=0, lib=None):
     if rc != 0:
         raise RTError(rc, f"rt_debug_eval_op(op {op}, form {form})")
     return out, list(flags)
+
+
+def debug_eval_shade_op(ctx, op, form, rows, device=0, lib=None):
+    """rt_debug_eval_shade_op (rt_debug.h): the render kernels' sampling, light, camera or shading
+    operation `op` (RT_SOP_*) in device form `form` over rows ([n, 20] float32), one lane per row, on the
+    scene a RenderContext uploaded.  Returns the words [n, 12] uint32; device < 0 runs the input guard
+    alone (ctx may be None) and returns None."""
+    import numpy as np
+    L = lib or (ctx._L if ctx is not None else amd())
+    rows = np.ascontiguousarray(rows, np.float32)
+    n = rows.shape[0]
+    if rows.shape != (n, 20):
+        raise ValueError("rows must be [n, 20] float32")
+    out = np.zeros((n, 12), np.uint32)
+    h = ctx._h if ctx is not None else None
+    rc = L.rt_debug_eval_shade_op(h, device, op, form, rows.ctypes.data_as(c_float_p), n,
+                                  out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint32)))
+    if rc != 0:
+        raise RTError(rc, L.rt_last_error(h).decode() if h is not None else f"rt_debug_eval_shade_op(op {op}, form {form})")
+    return out if device >= 0 else None
