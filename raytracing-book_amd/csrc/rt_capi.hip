@@ -31,19 +31,9 @@ void set_all_frames(rt_ctx* c, int n) {
     c->tile_frames.clear();
 }
 
-// the device's copies of the scene, its image, counters and stripe in the kernel arguments
+// the device's copies of the scene (bind_scene), its image, counters and stripe in the kernel arguments
 void bind_device(const rt_ctx* c, const Device& d, rt_kernel_args& a) {
-    a.nodes = (const rt_dnode*)d.nodes.ptr;
-    a.spheres = (const rt_sphere*)d.spheres.ptr;
-    a.quads = (const rt_quad*)d.quads.ptr;
-    a.boxes = (const rt_box*)d.boxes.ptr;
-    a.dquads = (const float4*)d.dquads.ptr;
-    a.dboxes = (const float4*)d.dboxes.ptr;
-    a.dboxc = (const float4*)d.dboxc.ptr;
-    a.perlin_pk = a.perlin_packed ? (const float4*)d.perlin_pk.ptr : nullptr;
-    a.media = (const rt_medium*)d.media.ptr;
-    a.lights = (const int32_t*)d.lights.ptr;
-    for (int t = 0; t < 8; t++) a.tex[t].data = d.tex[t].ptr;
+    bind_scene(d, a);
     a.image = d.image_ptr;
     a.stats = (unsigned long long*)d.stats.ptr;
     a.census = (unsigned*)d.census.ptr;

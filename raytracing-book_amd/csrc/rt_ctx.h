@@ -200,6 +200,21 @@ inline int ensure(rt_ctx* c, Device& d, DevBuf& b, size_t n) {
     return RT_OK;
 }
 
+// the device's copies of the scene in the kernel arguments (a.perlin_packed decides perlin_pk)
+inline void bind_scene(const Device& d, rt_kernel_args& a) {
+    a.nodes = (const rt_dnode*)d.nodes.ptr;
+    a.spheres = (const rt_sphere*)d.spheres.ptr;
+    a.quads = (const rt_quad*)d.quads.ptr;
+    a.boxes = (const rt_box*)d.boxes.ptr;
+    a.dquads = (const float4*)d.dquads.ptr;
+    a.dboxes = (const float4*)d.dboxes.ptr;
+    a.dboxc = (const float4*)d.dboxc.ptr;
+    a.perlin_pk = a.perlin_packed ? (const float4*)d.perlin_pk.ptr : nullptr;
+    a.media = (const rt_medium*)d.media.ptr;
+    a.lights = (const int32_t*)d.lights.ptr;
+    for (int t = 0; t < 8; t++) a.tex[t].data = d.tex[t].ptr;
+}
+
 // validate(SceneState&) of rt_args.h with its error text in the context
 inline int validate(rt_ctx* c) { return validate(*c, &c->err); }
 // rt_comm.hip (the RCCL table and its state stay in that unit)

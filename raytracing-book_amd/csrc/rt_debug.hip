@@ -13,6 +13,36 @@
 
 using namespace rt_impl;
 
+namespace {
+
+// A device buffer of one evaluation call, freed when the call returns.  Each step says whether it
+// succeeded; the callers chain them and report one RT_ERR_DEVICE.
+struct Scratch {
+    void* p = nullptr;
+    Scratch() = default;
+    Scratch(const Scratch&) = delete;
+    Scratch& operator=(const Scratch&) = delete;
+    ~Scratch() {
+        if (p) (void)hipFree(p);
+    }
+    bool alloc(size_t bytes) { return hipMalloc(&p, bytes) == hipSuccess; }
+    bool alloc_zero(size_t bytes) { return alloc(bytes) && hipMemset(p, 0, bytes) == hipSuccess; }
+    bool upload(const void* src, size_t bytes) { return upload_rows(src, bytes, 1, 1); }
+    // rows 0..n-1 of `row` bytes, padded to npad rows (whole waves) with copies of the last row
+    bool upload_rows(const void* src, size_t row, int n, int npad) {
+        if (!alloc(row * (size_t)npad) || hipMemcpy(p, src, row * (size_t)n, hipMemcpyHostToDevice) != hipSuccess)
+            return false;
+        for (int i = n; i < npad; i++)
+            if (hipMemcpy((char*)p + row * (size_t)i, (const char*)src + row * (size_t)(n - 1), row,
+                          hipMemcpyHostToDevice) != hipSuccess)
+                return false;
+        return true;
+    }
+    bool download(void* dst, size_t bytes) const { return hipMemcpy(dst, p, bytes, hipMemcpyDeviceToHost) == hipSuccess; }
+};
+
+}  // namespace
+
 extern "C" {
 
 // ---- debug / test hooks (rt_debug.h)
@@ -20,19 +50,12 @@ int rt_debug_eval_builtin(int device, int fn, const float* x, const float* y, fl
     if (!x || !out || n < 0) return RT_ERR_INVALID_ARG;
     if (n == 0) return RT_OK;
     if (hipSetDevice(device) != hipSuccess) return RT_ERR_DEVICE;
-    float *dx = nullptr, *dy = nullptr, *dout = nullptr;
-    size_t b = (size_t)n * 4;
-    int rc = RT_OK;
-    if (hipMalloc(&dx, b) != hipSuccess || hipMalloc(&dout, b) != hipSuccess || (y && hipMalloc(&dy, b) != hipSuccess))
-        rc = RT_ERR_DEVICE;
-    if (!rc && hipMemcpy(dx, x, b, hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_DEVICE;
-    if (!rc && y && hipMemcpy(dy, y, b, hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_DEVICE;
-    if (!rc && rt_launch_eval_builtin(fn, dx, dy, dout, n, nullptr)) rc = RT_ERR_DEVICE;
-    if (!rc && hipMemcpy(out, dout, b, hipMemcpyDeviceToHost) != hipSuccess) rc = RT_ERR_DEVICE;
-    if (dx) (void)hipFree(dx);
-    if (dy) (void)hipFree(dy);
-    if (dout) (void)hipFree(dout);
-    return rc;
+    const size_t b = (size_t)n * 4;
+    Scratch dx, dy, dout;
+    const bool ok = dx.upload(x, b) && (!y || dy.upload(y, b)) && dout.alloc(b) &&
+                    !rt_launch_eval_builtin(fn, (const float*)dx.p, (const float*)dy.p, (float*)dout.p, n, nullptr) &&
+                    dout.download(out, b);
+    return ok ? RT_OK : RT_ERR_DEVICE;
 }
 
 // The host half prepares the device records with the uploads' own functions (rt_prep.h, rt_args.h) and
@@ -98,48 +121,28 @@ int rt_debug_eval_op(int device, int op, int form, const void* recs, size_t rec_
     if (device < 0 || n == 0) return RT_OK;
 
     if (hipSetDevice(device) != hipSuccess) return RT_ERR_DEVICE;
-    void *d_rec = nullptr, *d_rows = nullptr, *d_out = nullptr, *d_tex = nullptr, *d_args = nullptr;
-    const size_t rows_b = (size_t)npad * RT_OPS_ROW_F * sizeof(float), out_b = (size_t)npad * RT_OPS_OUT_W * 4;
-    int rc = RT_OK;
-    auto up = [&](void** d, const void* src, size_t row, size_t bytes_dev) {   // rows 0..n-1, then the last row again
-        if (rc || !bytes_dev) return;
-        if (hipMalloc(d, bytes_dev) != hipSuccess) { rc = RT_ERR_DEVICE; return; }
-        if (hipMemcpy(*d, src, row * (size_t)n, hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_DEVICE;
-        for (int i = n; i < npad && !rc; i++)
-            if (hipMemcpy((char*)*d + row * (size_t)i, (const char*)src + row * (size_t)(n - 1), row,
-                          hipMemcpyHostToDevice) != hipSuccess)
-                rc = RT_ERR_DEVICE;
-    };
-    up(&d_rows, rows, RT_OPS_ROW_F * sizeof(float), rows_b);
-    if (rec_row) up(&d_rec, rec_src, rec_row, rec_row * (size_t)npad);
-    if (!rc && hipMalloc(&d_out, out_b) != hipSuccess) rc = RT_ERR_DEVICE;
-    if (!rc && hipMemset(d_out, 0, out_b) != hipSuccess) rc = RT_ERR_DEVICE;
+    Scratch d_rec, d_rows, d_out, d_tex, d_args;
+    bool ok = d_rows.upload_rows(rows, RT_OPS_ROW_F * sizeof(float), n, npad) &&
+              (!rec_row || d_rec.upload_rows(rec_src, rec_row, n, npad)) &&
+              d_out.alloc_zero((size_t)npad * RT_OPS_OUT_W * 4);
     // the argument block the texture functions read: slot 0's texture in global memory, no LDS tables
-    rt_kernel_args* a = new rt_kernel_args();
-    std::memset(a, 0, sizeof(*a));
-    a->perlin_slot = a->perlin_lds = a->media_lds = a->sph_lds = a->sph_mat_lds = a->box_mat_lds = a->tex_lds =
-        a->box_cmp_lds = a->leaf_lds = -1;
+    rt_kernel_args a;
+    std::memset(&a, 0, sizeof(a));
+    a.perlin_slot = -1;
+    clear_lds_tables(a, LDS_LEAF);   // (tex_lds_off[] stays 0: read only where tex_lds >= 0)
     if (op == RT_OP_PERLIN || op == RT_OP_TEXTURE) {
         const bool pk = op == RT_OP_PERLIN && form == 1;
-        const void* src = pk ? (const void*)tp.pk.data() : tp.src;
-        const size_t b = pk ? tp.pk.size() * sizeof(float4) : tp.bytes;
-        if (!rc && hipMalloc(&d_tex, b) != hipSuccess) rc = RT_ERR_DEVICE;
-        if (!rc && hipMemcpy(d_tex, src, b, hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_DEVICE;
-        a->tex[0].data = d_tex;
-        a->tex[0].w = tex_w;
-        a->tex[0].h = tex_h;
-        a->tex[0].is_float = tex_format == RT_TEX_R32F;
+        ok = ok && (pk ? d_tex.upload(tp.pk.data(), tp.pk.size() * sizeof(float4)) : d_tex.upload(tp.src, tp.bytes));
+        a.tex[0].data = d_tex.p;
+        a.tex[0].w = tex_w;
+        a.tex[0].h = tex_h;
+        a.tex[0].is_float = tex_format == RT_TEX_R32F;
     }
-    if (!rc && hipMalloc(&d_args, sizeof(*a)) != hipSuccess) rc = RT_ERR_DEVICE;
-    if (!rc && hipMemcpy(d_args, a, sizeof(*a), hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_DEVICE;
-    delete a;
-    if (!rc && rt_launch_eval_op((const rt_kernel_args*)d_args, op, form, op == RT_OP_PERLIN ? d_tex : d_rec,
-                                 (const float*)d_rows, d_out, npad, nullptr))
-        rc = RT_ERR_DEVICE;
-    if (!rc && hipMemcpy(out, d_out, (size_t)n * RT_OPS_OUT_W * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = RT_ERR_DEVICE;
-    for (void* p : {d_rec, d_rows, d_out, d_tex, d_args})
-        if (p) (void)hipFree(p);
-    return rc;
+    ok = ok && d_args.upload(&a, sizeof(a)) &&
+         !rt_launch_eval_op((const rt_kernel_args*)d_args.p, op, form, op == RT_OP_PERLIN ? d_tex.p : d_rec.p,
+                            (const float*)d_rows.p, d_out.p, npad, nullptr) &&
+         d_out.download(out, (size_t)n * RT_OPS_OUT_W * 4);
+    return ok ? RT_OK : RT_ERR_DEVICE;
 }
 
 // The host half checks the rows (the rejection loops never end on NaN draws; a shade row must name
@@ -181,36 +184,19 @@ int rt_debug_eval_shade_op(rt_ctx* c, int device, int op, int form, const float*
     if (n == 0) return RT_OK;
     rt_kernel_args a;
     if ((r = scene_args(*c, a, &c->err))) return r;
-    a.perlin_lds = a.media_lds = a.sph_lds = a.sph_mat_lds = a.box_mat_lds = a.tex_lds = a.box_cmp_lds = a.leaf_lds = -1;
-    for (int& o : a.tex_lds_off) o = -1;
+    clear_lds_tables(a, LDS_ALL);
     Device& d = c->devs[0];
     HIPCHK(c, hipSetDevice(d.id));
     HIPCHK(c, hipStreamSynchronize(d.stream));
-    a.spheres = (const rt_sphere*)d.spheres.ptr;
-    a.quads = (const rt_quad*)d.quads.ptr;
-    a.boxes = (const rt_box*)d.boxes.ptr;
-    a.dquads = (const float4*)d.dquads.ptr;
-    a.media = (const rt_medium*)d.media.ptr;
-    a.lights = (const int32_t*)d.lights.ptr;
-    for (int t = 0; t < 8; t++) a.tex[t].data = d.tex[t].ptr;
+    bind_scene(d, a);
     const int npad = (n + 63) / 64 * 64;
-    const size_t row_b = RT_SOP_ROW_F * sizeof(float), out_b = (size_t)npad * RT_SOP_OUT_W * 4;
-    std::vector<float> padded((size_t)npad * RT_SOP_ROW_F);   // rows 0..n-1, then the last row again
-    for (int i = 0; i < npad; i++) std::memcpy(&padded[(size_t)i * RT_SOP_ROW_F], rows + (size_t)std::min(i, n - 1) * RT_SOP_ROW_F, row_b);
-    void *d_rows = nullptr, *d_out = nullptr, *d_args = nullptr;
-    int rc = RT_OK;
-    if (hipMalloc(&d_rows, row_b * (size_t)npad) != hipSuccess || hipMalloc(&d_out, out_b) != hipSuccess ||
-        hipMalloc(&d_args, sizeof(a)) != hipSuccess)
-        rc = RT_ERR_DEVICE;
-    if (!rc && hipMemcpy(d_rows, padded.data(), row_b * (size_t)npad, hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_DEVICE;
-    if (!rc && hipMemset(d_out, 0, out_b) != hipSuccess) rc = RT_ERR_DEVICE;
-    if (!rc && hipMemcpy(d_args, &a, sizeof(a), hipMemcpyHostToDevice) != hipSuccess) rc = RT_ERR_DEVICE;
-    if (!rc && rt_launch_eval_shade_op((const rt_kernel_args*)d_args, op, form, (const float*)d_rows, d_out, npad, nullptr))
-        rc = RT_ERR_DEVICE;
-    if (!rc && hipMemcpy(out, d_out, (size_t)n * RT_SOP_OUT_W * 4, hipMemcpyDeviceToHost) != hipSuccess) rc = RT_ERR_DEVICE;
-    for (void* p : {d_rows, d_out, d_args})
-        if (p) (void)hipFree(p);
-    return rc ? set_err(c, rc, "rt_debug_eval_shade_op: a HIP call failed") : RT_OK;
+    Scratch d_rows, d_out, d_args;
+    const bool ok = d_rows.upload_rows(rows, RT_SOP_ROW_F * sizeof(float), n, npad) &&
+                    d_out.alloc_zero((size_t)npad * RT_SOP_OUT_W * 4) && d_args.upload(&a, sizeof(a)) &&
+                    !rt_launch_eval_shade_op((const rt_kernel_args*)d_args.p, op, form, (const float*)d_rows.p, d_out.p,
+                                             npad, nullptr) &&
+                    d_out.download(out, (size_t)n * RT_SOP_OUT_W * 4);
+    return ok ? RT_OK : set_err(c, RT_ERR_DEVICE, "rt_debug_eval_shade_op: a HIP call failed");
 }
 
 int rt_debug_read_samples(rt_ctx* c, float* out, size_t cap_floats, int* n_frames) {

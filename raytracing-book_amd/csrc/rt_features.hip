@@ -37,13 +37,12 @@ __global__ void __launch_bounds__(256) features_kernel(const KP* __restrict__ Pp
     const int x = (tile % tiles_x) * 8 + (lane & 7), y = (tile / tiles_x) * 8 + (lane >> 3);
     if (x >= W || y >= H) return;
     const size_t px = (size_t)y * W + x;
-    // the render's pbase (rt_kernel.hip render_stream) with no sub-pixel offset, from a pinhole
-    const rt_camera_ubo& C = P.cam;
+    // the pixel's base point with no sub-pixel offset, from a pinhole
     const float fx = (float)x, fy = (float)y;
-    const v3 coord = add3(add3(ld3(C.up_left), scale3(ld3(C.pixel_delta_u), fx)), scale3(ld3(C.pixel_delta_v), fy));
-    const v3 o = ld3(C.camera_pos), d = sub3(coord, o);
+    const v3 o = ld3(P.cam.camera_pos), d = sub3(pixel_base(P.cam, fx, fy), o);
     const float time = 0.0f;
 
+    // a new walk's set-up as rt_kernel.hip render_stream writes it out (its BEGIN block; kept in step by hand)
     Hit h;
     h.t = 0.0f; h.tif = 0;
     h.uv_kind_idx = 0; h.uv_a = 0.0f; h.uv_b = 0.0f;
@@ -76,43 +75,17 @@ __global__ void __launch_bounds__(256) features_kernel(const KP* __restrict__ Pp
         ai[px] = make_float4(P.background[0], P.background[1], P.background[2], __uint_as_float(RT_FEATURE_MISS));
         return;
     }
-    // the hit record as shade() forms it (rt_kernel_common.h), from the records in global memory
+    // shade()'s hit record from the records in global memory (every LDS table is off); its medium
+    // branch is unreachable here: media slots are cleared before the leaf tests
     const float t = tmax;
     const v3 p = add3(o, scale3(d, t));
-    const int h_type = h.tif & 0xF, h_face = (h.tif >> 4) & 0x7, h_idx = (int)((unsigned)h.tif >> 16);
-    v3 normal, emis = mk3s(0.0f);
-    bool front;
-    int material, tex_id;
-    if (h_type == RT_MODEL_SPHERE) {
-        const float4* sp = reinterpret_cast<const float4*>(P.spheres + h_idx);
-        const float4 A = ldg(sp), B = ldg(sp + 1), Cm = ldg(sp + 2);
-        const v3 center = add3(f3(A), scale3(f3(B), time));
-        const v3 on = divs3(sub3(p, center), B.w);
-        front = g_dot(d, on) < 0.0f;
-        normal = front ? on : neg3(on);
-        material = __float_as_int(Cm.w);
-        tex_id = __float_as_int(A.w);
-        if (front) emis = f3(Cm);
-    } else {   // quad, or box face h_face (material, texture and emission of quads[0])
-        const float4* q0 = (h_type == RT_MODEL_QUAD) ? reinterpret_cast<const float4*>(P.quads + h_idx)
-                                                    : reinterpret_cast<const float4*>(P.boxes + h_idx);
-        const v3 n = f3(ldg(q0 + 5 * h_face));
-        front = g_dot(d, n) < 0.0f;
-        normal = front ? n : neg3(n);
-        material = __float_as_int(ldg(q0 + 1).w);
-        tex_id = __float_as_int(ldg(q0 + 2).w);
-        if (front) emis = f3(ldg(q0 + 4));
-    }
+    const HitSurface hs = hit_surface<false, false>(P, h, d, p, time);
     // this hit's uv as after_trace() leaves it: the walk's last accepted hit is its closest
-    UvSrc uvs;
-    const bool sph = (h.uv_kind_idx >> 16) == 1;
-    const v3 up = add3(o, scale3(d, h.uv_a));
-    uvs.kind_idx = h.uv_kind_idx;
-    uvs.a = sph ? up.x : h.uv_a;
-    uvs.b = sph ? up.y : h.uv_b;
-    uvs.c = sph ? up.z : 0.0f;
-    const int mid = (material >> 16) & 0xFFFF;
-    const v3 alb = mid == RT_MAT_DIFFUSE_LIGHT ? emis : texture_color<false, false>(P, p, tex_id, uvs, time);
+    UvSrc uvs = {0, 0.0f, 0.0f, 0.0f};
+    walk_uv(h, o, d, uvs);
+    const int mid = (hs.material >> 16) & 0xFFFF;
+    const v3 alb = mid == RT_MAT_DIFFUSE_LIGHT ? hs.emis : texture_color<false, false>(P, p, hs.tex_id, uvs, time);
+    const v3 normal = hs.normal;
     nd[px] = make_float4(normal.x, normal.y, normal.z, t);
     ai[px] = make_float4(alb.x, alb.y, alb.z, __uint_as_float((uint32_t)h.tif));
 }
@@ -163,19 +136,10 @@ int rt_render_features(rt_ctx* c) {
     // the pass's argument block: the scene's records in global memory, no LDS table, no box pre-test
     rt_kernel_args a;
     std::memset(&a, 0, sizeof(a));
-    a.perlin_slot = a.perlin_lds = a.media_lds = a.sph_lds = a.sph_mat_lds = a.box_mat_lds = a.tex_lds = a.box_cmp_lds =
-        a.leaf_lds = -1;
-    for (int& o : a.tex_lds_off) o = -1;
-    a.nodes = (const rt_dnode*)d.nodes.ptr;
-    a.spheres = (const rt_sphere*)d.spheres.ptr;
-    a.quads = (const rt_quad*)d.quads.ptr;
-    a.boxes = (const rt_box*)d.boxes.ptr;
-    a.dquads = (const float4*)d.dquads.ptr;
-    a.dboxes = (const float4*)d.dboxes.ptr;
-    a.dboxc = (const float4*)d.dboxc.ptr;
-    a.media = (const rt_medium*)d.media.ptr;
+    a.perlin_slot = -1;
+    clear_lds_tables(a, LDS_ALL);
+    bind_scene(d, a);
     for (int t = 0; t < 8; t++) {
-        a.tex[t].data = d.tex[t].ptr;
         a.tex[t].w = c->tex_w[t];
         a.tex[t].h = c->tex_h[t];
         a.tex[t].is_float = c->tex_format[t] == RT_TEX_R32F;

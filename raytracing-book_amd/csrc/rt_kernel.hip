@@ -24,7 +24,7 @@
 //     are divided independently before the sequential acceptance; a medium's
 //     two boundary hits share one quadratic.
 // rand() consumption order is identical to the reference.
-#include "rt_kernel_common.h"
+#include "rt_kernel_launch.h"
 
 namespace {
 
@@ -290,8 +290,7 @@ __device__ __forceinline__ void render_stream(const KP& P, const float4* __restr
                     fy = (float)y;
                     unsigned long long t0 = STATS ? clock64() : 0;
                     if (STATS) st_lanes(st, ST_START_IT, ST_START_LN);
-                    const v3 pbase = add3(add3(ld3(C.up_left), scale3(ld3(C.pixel_delta_u), fx)),
-                                          scale3(ld3(C.pixel_delta_v), fy));
+                    const v3 pbase = pixel_base(C, fx, fy);
                     start_path(P, S, P.first_frame + f, P.rand_factors[f], fx, fy, pbase);
                     if (STATS) st_add(st, ST_START_CYC, clock64() - t0);
                     if (P.max_depth <= 0) {   // the loop never runs: final_color vec3(0)
@@ -312,7 +311,9 @@ __device__ __forceinline__ void render_stream(const KP& P, const float4* __restr
             if (__ballot(fin)) break;   // count these before claiming more (below)
         }
         RT_ST_PART(ST_CLAIM_CYC)
-        // a new walk (bounce(): depth, a zero direction hits nothing, compute.glsl:226-229)
+        // a new walk (bounce(): depth, a zero direction hits nothing, compute.glsl:226-229).  Its set-up
+        // -- h cleared, inv, a, and lane_exact in the rounds -- is written out in rt_features.hip
+        // features_kernel too: one helper for both changed these kernels' instructions
         if (status == RT_SM_BEGIN) {
             S.depth++;
             h.t = 0.0f; h.tif = 0;

@@ -1,34 +1,50 @@
-// rt_kernel_common.h -- the device code both kernel translation units share (included once per
-// TU, inside its anonymous namespace): the GLSL restatement's primitives, leaf tests, link walks,
-// textures, sampling and shading, the ordered-chunk hand-off, the LDS staging and the persistent
-// launcher.  rt_kernel.hip builds the release structure on it (render_stream);
-// (rt_kernel_variants.hip, A/B library only, -DRT_AB_KNOBS) the other structures (one pixel per lane, threaded meta-word
-// nodes, the exact near-first walk) and their stats twins.  rand() consumption order is identical
-// to the reference.
+// rt_kernel_common.h -- the restated shader, the device code every kernel translation unit shares
+// (included once per TU, inside its anonymous namespace): the loads, rand(), the division forms, the
+// primitive and leaf tests, the link walks, textures, lights, shade() and start_path(), with the
+// statistics slots those call under STATS.  rt_kernel.hip builds the release structure on it
+// (render_stream); rt_kernel_variants.hip (A/B library only, -DRT_AB_KNOBS) the other structures
+// (one pixel per lane, threaded meta-word nodes, the exact near-first walk) and their stats twins;
+// both add rt_kernel_launch.h (chunk hand-off, LDS staging, launcher).  The first-hit pass
+// (rt_features.hip) and the op-by-op evaluators (rt_ops_eval.hip, rt_shade_eval.hip) call the same
+// functions from here alone.  rand() consumption order is identical to the reference.
 #pragma once
 
 #include <hip/hip_runtime.h>
 
-#include <algorithm>
-#include <cstdio>
-#include <cstdlib>
-
 #include "rt/rt_glsl.h"
 #include "rt_device.h"
-#include "rt_fold_step.h"
-#include "rt_plan.h"
 
+// ---- compile-time A/B switches (tools/build_variant_lib.sh <tag> -DNAME=0 builds the other form
+// for tools/lib_ab.py; the OPT bits of the kernel templates are rt_plan.h RT_OPT_*) ----
+// 0: the sphere-pair STD kernels walk with link_walk_part's exec-mask branches (BL only in the
+// compact-box STD kernels); 1 (scene 0: -0.8%, profiles/r06_ae_bl_spair_lib_ab.log)
+#ifndef RT_BL_SPAIR
+#define RT_BL_SPAIR 1
+#endif
+// a count, not a switch (0 builds a walk that takes no step): the BL walk's steps between the partial
+// walk's stop checks (link_walk_part); the other forms measured are 1, 3 and 4
+#ifndef RT_BL_STEPS
+#define RT_BL_STEPS 2
+#endif
+// 0: the scene-8 kernels' (RT_OPT_BOXQ, DESIGN §4 "Walk trim") leaf stage finds a slot record's LDS
+// address by a branch cascade instead of selects (leaf_prims_t)
+#ifndef RT_WT_DISPATCH
+#define RT_WT_DISPATCH 1
+#endif
+// 0: the same kernels without the first-leaf prologue (rt_kernel.hip render_stream, DESIGN §4 "First
+// leaf"), which tests a walk that starts at the spine's leaf where the walk begins
+#ifndef RT_WT_FIRST_LEAF
+#define RT_WT_FIRST_LEAF 1
+#endif
+// 0: the same kernels' shade() with the mixture as every other kernel has it, not the per-pass trim
+// (DESIGN §4 "Per-pass blocks") that drops the lights_random call when no light is registered
+#ifndef RT_PB_NOLIGHT
+#define RT_PB_NOLIGHT 1
+#endif
 
 namespace {
 
 typedef rt_kernel_args KP;
-
-// (the OPT bits of the kernel templates: rt_plan.h RT_OPT_*, with the table of instantiations)
-// the branchless walk (link_walk_part BL) in the sphere-pair STD kernels too (scene 0: -0.8%,
-// profiles/r06_ae_bl_spair_lib_ab.log); the compact-box STD kernels always
-#ifndef RT_BL_SPAIR
-#define RT_BL_SPAIR 1
-#endif
 
 // The kernels' dynamic LDS (render_persistent stages the BVH there, then the
 // Perlin table and the media records when P.perlin_lds / P.media_lds >= 0).
@@ -123,32 +139,6 @@ __device__ __forceinline__ void st_pred(unsigned long long* st, bool pred, int i
     }
 }
 
-// The leaf census (stats twin with P.census): one record per wave leaf round -- when it started,
-// how long it took, which wave, how many lanes were walking, and per prim type how many lanes
-// hold a slot-0 / slot-1 test -- so tools/leaf_census.py can count what a workgroup-wide queue
-// per prim type could have pooled.  Called by the lanes at a leaf (the first one writes).
-__device__ __forceinline__ void census_leaf(const KP& P, int gwave, uint32_t types, unsigned long long t0,
-                                            unsigned long long t1, int walking, unsigned long long* st) {
-    const uint32_t a = types & 7u, b = (types >> 4) & 0xFu;
-    uint32_t s0 = 0, s1 = 0;
-#pragma unroll
-    for (int k = 1; k <= 4; k++) {
-        s0 |= (uint32_t)__popcll(__ballot(a == (uint32_t)k)) << (8 * (k - 1));
-        s1 |= (uint32_t)__popcll(__ballot(b == (uint32_t)k)) << (8 * (k - 1));
-    }
-    if (first_active_lane()) {
-        const unsigned long long i = atomicAdd(&st[ST_CEN_N], 1ull);
-        if (gwave < P.census_waves && i < (unsigned long long)P.census_cap) {
-            unsigned* r = P.census + P.census_waves + ((size_t)gwave * P.census_cap + i) * RT_CENSUS_WORDS;
-            r[0] = (unsigned)t0;
-            r[1] = (unsigned)(t1 - t0);
-            r[2] = (unsigned)blockIdx.x | ((unsigned)(threadIdx.x >> 6) << 16) | ((unsigned)walking << 24);
-            r[3] = s0;
-            r[4] = s1;
-        }
-    }
-}
-
 __device__ __forceinline__ void st_small(unsigned long long* st, bool pred, int slot) {
     const int n = __popcll(__ballot(pred));
     if (n > 0 && n <= 8 && first_active_lane()) atomicAdd(&st[slot], 1ull);
@@ -164,24 +154,6 @@ __device__ __forceinline__ float rnd(float& rf, float px, float py) {
     v2 k = {12.9898f, 78.233f};
     return g_fract(g_sin(g_dot2(co, k)) * 43758.5453123f);
 }
-
-// The trimmed scene-8 kernels (the RT_OPT_BOXQ instantiations, DESIGN §4 "Walk trim"): the leaf stage
-// computes a slot record's LDS address by selects instead of a branch cascade (leaf_prims_t).
-// tools/build_variant_lib.sh builds the other form (-DRT_WT_DISPATCH=0) for tools/lib_ab.py.
-#ifndef RT_WT_DISPATCH
-#define RT_WT_DISPATCH 1
-#endif
-// The same kernels' first-leaf prologue (rt_kernel.hip render_stream, DESIGN §4 "First leaf"): a walk
-// that starts at the spine's leaf tests it where the walk begins.  -DRT_WT_FIRST_LEAF=0: compiled out.
-#ifndef RT_WT_FIRST_LEAF
-#define RT_WT_FIRST_LEAF 1
-#endif
-// The same kernels' per-pass trims (DESIGN §4 "Per-pass blocks"): the code a wave runs once per pass.
-// RT_PB_NOLIGHT: shade()'s mixture without the lights_random call when no light is registered.
-// -DRT_PB_NOLIGHT=0: the mixture as every other kernel has it.
-#ifndef RT_PB_NOLIGHT
-#define RT_PB_NOLIGHT 1
-#endif
 
 // Source of hit_record.uv (compute.glsl:62): the last successful sphere or quad
 // hit of the sample (it persists across bounces; media do not write it).
@@ -975,11 +947,8 @@ __device__ __forceinline__ uint32_t link_walk(const NodeSrc& ns, uint32_t nx, v3
 // -0.4% (with the stop check every 2 steps, RT_BL_STEPS, another -0.2..-0.3%), scene 0 -0.8% (with it);
 // scene 6's kernel (a 7-node tree: short walks) +1.8%, so there it stays off
 // (profiles/r06_x_node_branchless_lib_ab.log, r06_ae_bl_spair_lib_ab.log; round 3: -0.5 / -0.2 / +1.7%).
-// the BL walk's steps between the partial walk's stop checks: 2 (scene 8 -0.2% at 1080p, -0.3% at
-// 4K against 3; 1 +1.8%, 4 +0.8%: profiles/r06_ab_bl_steps{,_4k}_lib_ab.log, r06_aa_lib_ab.log)
-#ifndef RT_BL_STEPS
-#define RT_BL_STEPS 2
-#endif
+// the BL walk's steps between the partial walk's stop checks (RT_BL_STEPS): 2 (scene 8 -0.2% at 1080p,
+// -0.3% at 4K against 3; 1 +1.8%, 4 +0.8%: profiles/r06_ab_bl_steps{,_4k}_lib_ab.log, r06_aa_lib_ab.log)
 template <bool EXACT, bool STATS, bool TL = false, bool BL = false>
 __device__ __forceinline__ uint32_t link_walk_part(const NodeSrc& ns, uint32_t nx, v3 o, v3 inv, float tmin,
                                                    float tmax, int need, unsigned long long* st) {
@@ -1407,26 +1376,16 @@ __device__ __forceinline__ v3 lights_random(const KP& P, v3 o, float& rf, float 
 }
 
 // ------------------------------------------------------------- ray_color
-// Per-lane path state carried between bounces (ray_color's locals).
-struct Path {
-    v3 o, d, acc;
-    float time, rf;
-    UvSrc uvs;
-    int depth;
+// hit_record of the closest hit h at p along d (hitting.glsl:40-42,189-190, compute.glsl:197-224): the normal
+// against the ray, the front face, and the surface's material word, texture id and emission (zero
+// from a back face).  shade() and the first-hit pass (rt_features.hip) form it here.
+struct HitSurface {
+    v3 normal, emis;
+    bool front;
+    int material, tex_id;
 };
-
-// The shading half of ray_color's loop body (compute.glsl:310-339) for a hit.
-// Returns true when the path ended, with its color in `result`.
-// STD (RT_OPT_STD kernels): the shading tables are staged -- every sphere's, and with PK_INLINE (the
-// compact-box kernels) every box's; the texture descriptors
-// PB (the RT_OPT_BOXQ kernels): the per-pass trims (RT_PB_*, DESIGN §4 "Per-pass blocks").
-template <bool PK_INLINE = false, bool STATS = false, bool STD = false, bool PB = false>
-__device__ __forceinline__ bool shade(const KP& P, Path& S, const Hit& h, float px, float py, v3& result,
-                                      unsigned long long* st = nullptr) {
-    unsigned long long c0 = STATS ? clock64() : 0;
-    v3 d = S.d;
-    // hit_record of the closest hit: p = ray.o + ray.dir*t (hitting.glsl:39,104,188)
-    v3 p = add3(S.o, scale3(d, h.t));
+template <bool PK_INLINE = false, bool STD = false>
+__device__ __forceinline__ HitSurface hit_surface(const KP& P, const Hit& h, v3 d, v3 p, float time) {
     v3 normal;
     bool front;
     int material, tex_id;
@@ -1444,7 +1403,7 @@ __device__ __forceinline__ bool shade(const KP& P, Path& S, const Hit& h, float 
             B = ldg(sp + 1);
             C = ldg(sp + 2);
         }
-        v3 center = add3(f3(A), scale3(f3(B), S.time));
+        v3 center = add3(f3(A), scale3(f3(B), time));
         v3 on = divs3(sub3(p, center), B.w);
         front = g_dot(d, on) < 0.0f;
         normal = front ? on : neg3(on);
@@ -1485,6 +1444,39 @@ __device__ __forceinline__ bool shade(const KP& P, Path& S, const Hit& h, float 
         tex_id = __float_as_int(ldg(q0 + 2).w);
         if (front) emis = f3(ldg(q0 + 4));
     }
+    HitSurface r;
+    r.normal = normal;
+    r.emis = emis;
+    r.front = front;
+    r.material = material;
+    r.tex_id = tex_id;
+    return r;
+}
+
+// Per-lane path state carried between bounces (ray_color's locals).
+struct Path {
+    v3 o, d, acc;
+    float time, rf;
+    UvSrc uvs;
+    int depth;
+};
+
+// The shading half of ray_color's loop body (compute.glsl:310-339) for a hit.
+// Returns true when the path ended, with its color in `result`.
+// STD (RT_OPT_STD kernels): the shading tables are staged -- every sphere's, and with PK_INLINE (the
+// compact-box kernels) every box's; the texture descriptors
+// PB (the RT_OPT_BOXQ kernels): the per-pass trims (RT_PB_*, DESIGN §4 "Per-pass blocks").
+template <bool PK_INLINE = false, bool STATS = false, bool STD = false, bool PB = false>
+__device__ __forceinline__ bool shade(const KP& P, Path& S, const Hit& h, float px, float py, v3& result,
+                                      unsigned long long* st = nullptr) {
+    unsigned long long c0 = STATS ? clock64() : 0;
+    v3 d = S.d;
+    // hit_record of the closest hit: p = ray.o + ray.dir*t (hitting.glsl:39,104,188)
+    v3 p = add3(S.o, scale3(d, h.t));
+    const HitSurface hs = hit_surface<PK_INLINE, STD>(P, h, d, p, S.time);
+    const v3 normal = hs.normal, emis = hs.emis;
+    const bool front = hs.front;
+    const int material = hs.material, tex_id = hs.tex_id;
     // A solid texture's colour (texture_color's first case) read here, before the scatter, so that its
     // two dependent LDS reads overlap the scatter's arithmetic; the same texel, so the same value.
     // Not in the compact-box kernels (PK_INLINE, scene 8): there +0.5%, scene 6 -1.5%, scene 0 -0.7%
@@ -1602,6 +1594,8 @@ __device__ __forceinline__ bool shade(const KP& P, Path& S, const Hit& h, float 
                 return true;
             }
         } else {
+            // (a copy of the generic mixture below this block, kept in step with it by hand: one helper
+            // for both changed the branch structure of every render kernel)
             if (rnd(rf, px, py) < 0.5f) d = lights_random(P, p, rf, px, py);
             float lpdf = (P.lights_count > 0) ? lights_pdf_value(P, p, d, S.time) : 0.0f;
             float mpdf;
@@ -1629,6 +1623,7 @@ __device__ __forceinline__ bool shade(const KP& P, Path& S, const Hit& h, float 
         S.d = d;
         return false;
     }
+    // the generic mixture (compute.glsl:322-337); the PB block's lit branch above copies it
     if (rnd(rf, px, py) < 0.5f) d = lights_random(P, p, rf, px, py);
     float lpdf = (P.lights_count > 0) ? lights_pdf_value(P, p, d, S.time) : 0.0f;
     float mpdf;
@@ -1661,24 +1656,35 @@ __device__ __forceinline__ bool shade(const KP& P, Path& S, const Hit& h, float 
     return false;
 }
 
+// The uv a walk left (compute.glsl:62) handed over to the path's uv source: the walk's last sphere
+// or quad hit, none when it wrote none.
+__device__ __forceinline__ void walk_uv(const Hit& h, v3 o, v3 d, UvSrc& uvs) {
+    if (h.uv_kind_idx != 0) {
+        bool sph = (h.uv_kind_idx >> 16) == 1;
+        v3 up = add3(o, scale3(d, h.uv_a));   // the sphere hit's p (hitting.glsl:39)
+        uvs.kind_idx = h.uv_kind_idx;
+        uvs.a = sph ? up.x : h.uv_a;
+        uvs.b = sph ? up.y : h.uv_b;
+        uvs.c = sph ? up.z : uvs.c;
+    }
+}
+
 // The rest of ray_color's loop body after the walk (compute.glsl:308-340): the
-// uv the walk left (compute.glsl:62), the background on a miss, else shade().
+// uv the walk left, the background on a miss, else shade().
 template <bool PK_INLINE = false, bool STATS = false, bool STD = false, bool PB = false>
 __device__ __forceinline__ bool after_trace(const KP& P, Path& S, const Hit& h, bool hit, float px, float py,
                                             v3& result, unsigned long long* st = nullptr) {
-    if (h.uv_kind_idx != 0) {
-        bool sph = (h.uv_kind_idx >> 16) == 1;
-        v3 up = add3(S.o, scale3(S.d, h.uv_a));   // the sphere hit's p (hitting.glsl:39)
-        S.uvs.kind_idx = h.uv_kind_idx;
-        S.uvs.a = sph ? up.x : h.uv_a;
-        S.uvs.b = sph ? up.y : h.uv_b;
-        S.uvs.c = sph ? up.z : S.uvs.c;
-    }
+    walk_uv(h, S.o, S.d, S.uvs);
     if (!hit) {
         result = mul3(S.acc, mk3(P.background[0], P.background[1], P.background[2]));
         return true;
     }
     return shade<PK_INLINE, STATS, STD, PB>(P, S, h, px, py, result, st);
+}
+
+// Pixel (fx, fy)'s base point on the viewport: start_path's `base`, the first-hit pass' centre ray.
+__device__ __forceinline__ v3 pixel_base(const rt_camera_ubo& C, float fx, float fy) {
+    return add3(add3(ld3(C.up_left), scale3(ld3(C.pixel_delta_u), fx)), scale3(ld3(C.pixel_delta_v), fy));
 }
 
 // Camera ray of frame `frame_count` (compute.glsl:345-350, random.glsl:19-30,82-100).
@@ -1714,128 +1720,6 @@ __device__ __forceinline__ void start_path(const KP& P, Path& S, int frame_count
     S.acc = mk3s(1.0f);
     S.depth = 0;
     S.uvs.kind_idx = 0; S.uvs.a = 0.0f; S.uvs.b = 0.0f; S.uvs.c = 0.0f;
-}
-
-// Ordered chunks (a launch over few tiles per resident wave, e.g. the stripe set
-// of one of N GPUs): the work unit is one 8x8 tile x one chunk of the launch's
-// frames, unit = chunk * n_tiles + tile, so chunk k of a tile is dequeued after
-// chunk k-1.  The wave that takes chunk k > 0 waits until chunk k-1 of its tile
-// is published, then continues that tile's running mean from the image: the
-// reference's per-frame formula in frame order, so the same bits as one chunk.
-// Publication follows the agent-scope release/acquire recipe of
-// cdna_hip_programming.md §6 G16: the producing wave's plain image stores,
-// vmcnt(0), release fence, vmcnt(0), then one relaxed agent-scope store of the
-// tile's chunk count; the consumer polls that word relaxed (with s_sleep), then
-// one acquire fence, then plain loads.  The unit it waits for was dequeued
-// earlier by a running wave that waits only on earlier units, so the chain ends
-// at chunk 0; the poll is still bounded (RT_CHUNK_WAIT_TICKS of the 100 MHz
-// real-time clock, P.chunk_wait_ticks: 30 s by default) and a timeout sets
-// P.fault, which rt_sync reports.
-typedef __attribute__((address_space(1))) unsigned gu32;   // global (never flat) accesses to shared words
-// tile and chunk are wave-uniform (readfirstlane): every lane polls / stores the
-// same word with the same value, so there is no lane-divergent control flow here
-__device__ __forceinline__ void wait_chunk(const KP& P, int tile, int chunk) {
-    const unsigned long long t0 = __builtin_amdgcn_s_memrealtime();
-    gu32* w = (gu32*)(P.tile_done + tile);
-    while (__builtin_amdgcn_readfirstlane(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) <
-           (unsigned)chunk) {
-        __builtin_amdgcn_s_sleep(2);
-        if (__builtin_amdgcn_s_memrealtime() - t0 >= P.chunk_wait_ticks) {
-            __hip_atomic_store((gu32*)P.fault, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            break;
-        }
-    }
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-}
-__device__ __forceinline__ void publish_chunk(const KP& P, int tile, int chunk) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __hip_atomic_store((gu32*)(P.tile_done + tile), (unsigned)(chunk + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// The link-format shapes' LDS staging (rt_capi.hip plans it; every workgroup once): the nodes
-// (all, or the two-level walk's top levels; LINK = false: the threaded meta-word nodes of the A/B
-// variant 30), the leaf records, the packed Perlin table, the media records with their sphere
-// boundaries, the spheres' (A, B) halves, the boxes' compact records and the shading tables.
-template <bool LINK, int BLOCK>
-__device__ __forceinline__ void stage_lds(const KP& P, float4* s_nodes, int tid) {
-    // link format: the nodes staged (all, or the two-level walk's top levels), then the leaf
-    // records when they are staged too; meta format: the threaded nodes
-    const float4* g = LINK ? P.lnodes : reinterpret_cast<const float4*>(P.nodes);
-    const int nf4 = LINK ? P.lds_node_f4 : 2 * P.n_nodes;
-    for (int k = tid; k < nf4; k += BLOCK) s_nodes[k] = g[k];
-    if (LINK && P.leaf_lds >= 0)
-        for (int k = tid; k < P.n_lnode_f4 - 2 * P.n_nodes; k += BLOCK)
-            s_nodes[P.leaf_lds + k] = g[2 * P.n_nodes + k];
-    if (P.perlin_lds >= 0)   // the packed Perlin table after the nodes (host-sized launch)
-        for (int k = tid; k < 256; k += BLOCK) s_nodes[P.perlin_lds + k] = ldg(P.perlin_pk + k);
-    if (P.media_lds >= 0) {   // per medium: (boundary idx, type, -1/density, phase), sphere A, B
-        for (int k = tid; k < 3 * P.n_media; k += BLOCK) {
-            const rt_medium& m = P.media[k / 3];
-            float4 v = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-            if (k % 3 == 0)
-                v = make_float4(__int_as_float(m.boundary_idx), __int_as_float(m.boundary_type), m.neg_inv_density,
-                                __int_as_float(m.phase_material));
-            else if (m.boundary_type == RT_MODEL_SPHERE)
-                v = reinterpret_cast<const float4*>(P.spheres + m.boundary_idx)[k % 3 - 1];
-            s_nodes[P.media_lds + k] = v;
-        }
-    }
-    if (P.sph_lds >= 0) {   // per sphere its first two float4 (center0 + texture, motion + radius)
-        const float4* sp = reinterpret_cast<const float4*>(P.spheres);
-        for (int k = tid; k < 2 * P.n_sph_lds; k += BLOCK) s_nodes[P.sph_lds + k] = ldg(sp + (k >> 1) * 3 + (k & 1));
-    }
-    if (P.box_cmp_lds >= 0)   // the boxes' compact records (box_test_compact)
-        for (int k = tid; k < RT_BOXC_F4 * P.n_box_lds; k += BLOCK) s_nodes[P.box_cmp_lds + k] = ldg(P.dboxc + k);
-    // the shading tables (P.sph_mat_lds / box_mat_lds / tex_lds, option shade_lds)
-    if (P.sph_mat_lds >= 0) {   // per sphere its third float4: emission, material
-        const float4* sp = reinterpret_cast<const float4*>(P.spheres);
-        for (int k = tid; k < P.n_sph_lds; k += BLOCK) s_nodes[P.sph_mat_lds + k] = ldg(sp + 3 * k + 2);
-    }
-    if (P.box_mat_lds >= 0) {   // per box quads[0]'s emission and material
-        for (int k = tid; k < P.n_box_lds; k += BLOCK) {
-            const float4* q0 = reinterpret_cast<const float4*>(P.boxes + k);
-            const float4 e = ldg(q0 + 4), m = ldg(q0 + 1);
-            s_nodes[P.box_mat_lds + k] = make_float4(e.x, e.y, e.z, m.w);
-        }
-    }
-    if (P.tex_lds >= 0) {   // per slot (w, h, is_float, texel offset), then the small slots' texels
-        if (tid < 8) {
-            const rt_dtex& T = P.tex[tid];
-            const int off = T.data ? P.tex_lds_off[tid] : -1;
-            s_nodes[P.tex_lds + tid] = make_float4(__int_as_float(T.data ? T.w : 0), __int_as_float(T.h),
-                                                   __int_as_float(T.is_float), __int_as_float(off));
-        }
-        for (int t = 0; t < 8; t++) {
-            const rt_dtex& T = P.tex[t];
-            if (P.tex_lds_off[t] < 0 || !T.data) continue;
-            const int words = T.w * T.h;
-            const uint32_t* src = reinterpret_cast<const uint32_t*>(T.data);
-            uint32_t* dst = reinterpret_cast<uint32_t*>(s_nodes + P.tex_lds_off[t]);
-            for (int k = tid; k < words; k += BLOCK) dst[k] = src[k];
-        }
-    }
-}
-
-template <typename K>
-int launch_persistent(K kernel, int block, size_t lds, const rt_kernel_args& a, const rt_kernel_args* d,
-                      hipStream_t st) {
-    int dev = 0, cus = 0, per_cu = 0;
-    if (hipGetDevice(&dev) != hipSuccess) return -1;
-    if (hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess) return -1;
-    if (lds > 64 * 1024 &&
-        hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            (int)lds) != hipSuccess)
-        return -1;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, kernel, block, lds) != hipSuccess || per_cu < 1)
-        per_cu = 1;
-    per_cu = per_cu > 2 ? 2 : per_cu;   // rt_resident_waves(): the per-wave buffers are sized for it
-    if ((long long)cus * per_cu * (block / 64) > (long long)rt_resident_waves()) return -1;
-    if (a.wbuf && (long long)cus * per_cu * (block / 64) > (long long)a.wbuf_waves) return -1;
-    hipLaunchKernelGGL(kernel, dim3(cus * per_cu), dim3(block), lds, st, d);
-    return 0;
 }
 
 }  // namespace

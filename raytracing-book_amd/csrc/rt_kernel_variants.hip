@@ -8,7 +8,7 @@
 #ifndef RT_AB_KNOBS
 #error "rt_kernel_variants.hip is the A/B library's translation unit (-DRT_AB_KNOBS)"
 #endif
-#include "rt_kernel_common.h"
+#include "rt_kernel_launch.h"
 
 namespace {
 

@@ -58,10 +58,7 @@ void plan_lds(const LdsIn& in, rt_kernel_args& a) {
     if (tl && !in.walk_frac) a.walk_frac = 32;
     size_t at = 0;
     a.lds_node_f4 = 0;
-    a.leaf_lds = -1;
-    a.perlin_lds = a.media_lds = a.sph_lds = a.box_cmp_lds = -1;
-    a.sph_mat_lds = a.box_mat_lds = a.tex_lds = -1;
-    for (int t = 0; t < 8; t++) a.tex_lds_off[t] = -1;
+    clear_lds_tables(a, LDS_ALL);
     if (meta) {
         at = node_f4;   // the threaded nodes (32 B each) from address 0 (rt_launch_render: META_LDS)
     } else if (!fast_walk && in.n_lnode_f4 > 0) {
@@ -168,8 +165,7 @@ KernelPlan plan_kernel(rt_kernel_args& a, bool ab) {
         }
         if (shape == RT_SHAPE_FAST_LDS || shape == RT_SHAPE_FAST_GLOBAL || shape == RT_SHAPE_META_GLOBAL) {
             if (shape == RT_SHAPE_META_GLOBAL) staged = 0;   // nothing else staged
-            a.perlin_lds = a.media_lds = a.sph_lds = a.box_cmp_lds = -1;
-            a.sph_mat_lds = a.box_mat_lds = a.tex_lds = -1;
+            clear_lds_tables(a, 0);   // (leaf_lds and tex_lds_off[] stay: nothing of these shapes reads them)
         }
     }
     const bool link = shape == RT_SHAPE_LINK_LDS || shape == RT_SHAPE_LINK_TL;

@@ -68,6 +68,20 @@ inline bool pooled_variant(int variant) { return variant == 0 || variant == 39; 
 // 8x8 tiles of `rows` rows of an image
 inline int tile_count(int width, int rows) { return ((width + 7) / 8) * ((rows + 7) / 8); }
 
+// The LDS tables of rt_kernel_args: their float4 offsets in the dynamic LDS, -1 = not staged (the shared
+// device functions then take their global-memory forms).  A table added to rt_kernel_args is listed here.
+constexpr int rt_kernel_args::* LDS_TABLES[] = {
+    &rt_kernel_args::perlin_lds,  &rt_kernel_args::media_lds,   &rt_kernel_args::sph_lds, &rt_kernel_args::box_cmp_lds,
+    &rt_kernel_args::sph_mat_lds, &rt_kernel_args::box_mat_lds, &rt_kernel_args::tex_lds};
+// No table staged.  LDS_LEAF: nor the leaf records (leaf_lds); LDS_TEXELS: nor any slot's texels (tex_lds_off[]).
+enum { LDS_LEAF = 1, LDS_TEXELS = 2, LDS_ALL = LDS_LEAF | LDS_TEXELS };
+inline void clear_lds_tables(rt_kernel_args& a, int also) {
+    for (int rt_kernel_args::* t : LDS_TABLES) a.*t = -1;
+    if (also & LDS_LEAF) a.leaf_lds = -1;
+    if (also & LDS_TEXELS)
+        for (int& o : a.tex_lds_off) o = -1;
+}
+
 struct KernelId {
     int block, opt;
 };

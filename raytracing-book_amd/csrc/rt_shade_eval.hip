@@ -46,11 +46,8 @@ __global__ void __launch_bounds__(256) eval_shade_op_kernel(const KP* __restrict
         put3(0, lights_random(P, o, rf, px, py));
         w[3] = __float_as_uint(rf);
     } else if (op == RT_SOP_CAMERA_RAY) {
-        // base as the render kernel writes it for pixel (px, py) (rt_kernel.hip render_stream)
-        const rt_camera_ubo& C = P.cam;
-        const v3 pbase = add3(add3(ld3(C.up_left), scale3(ld3(C.pixel_delta_u), px)), scale3(ld3(C.pixel_delta_v), py));
         Path S;
-        start_path(P, S, __float_as_int(r[19]), rf, px, py, pbase);
+        start_path(P, S, __float_as_int(r[19]), rf, px, py, pixel_base(P.cam, px, py));
         w[0] = __float_as_uint(S.time);
         put3(1, S.o);
         put3(4, S.d);

@@ -2,9 +2,9 @@
 # Builds raytracing-book_amd/lib/<tag>/librtamd.so from the working tree's kernel source with extra
 # compiler definitions (ablations and A/B forms, e.g. -DRT_ABL_UNITVEC1) and the working tree's
 # C ABI object, for tools/lib_ab.py.  usage: tools/build_variant_lib.sh <tag> <-Dflags...>
-# The scene-8 kernels' other forms (rt_kernel_common.h): -DRT_WT_DISPATCH=0 the leaf stage's record
-# address by a branch cascade, -DRT_WT_FIRST_LEAF=0 without the first-leaf prologue, -DRT_PB_NOLIGHT=0 the
-# mixture of shade() as every other kernel has it.
+# The kernels' compile-time A/B switches (RT_BL_SPAIR, RT_BL_STEPS, RT_WT_DISPATCH, RT_WT_FIRST_LEAF,
+# RT_PB_NOLIGHT) are one block at the top of raytracing-book_amd/csrc/rt_kernel_common.h, each with
+# what its other form builds: e.g. -DRT_WT_FIRST_LEAF=0.
 set -e
 TAG=$1; shift
 ROOT=$(cd "$(dirname "$0")/.." && pwd)

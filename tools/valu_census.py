@@ -12,7 +12,7 @@ import subprocess
 ROOT = __file__.rsplit("/tools/", 1)[0]
 PKG = ROOT + "/raytracing-book_amd"
 SRC = {"rt_kernel.hip": PKG + "/csrc/rt_kernel.hip", "rt_kernel_common.h": PKG + "/csrc/rt_kernel_common.h",
-       "rt_glsl.h": ROOT + "/include/rt/rt_glsl.h"}
+       "rt_kernel_launch.h": PKG + "/csrc/rt_kernel_launch.h", "rt_glsl.h": ROOT + "/include/rt/rt_glsl.h"}
 DEF = re.compile(r"^(?:template\s*<[^>]*>\s*)?(?:__device__|__global__|RT_HD|__host__)[^(;]*?\b(\w+)\s*\(")
 
 
