@@ -87,7 +87,20 @@ int rt_debug_eval_op(int device, int op, int form, const void* recs, size_t rec_
  *   RT_SOP_SHADE           shade<>             o, d, t, tif, time, px, py, rf,     ended; result r, g, b when ended,
  *                                              acc, UvSrc                          else o, d, acc (words 1..9);
  *                                                                                  word 10 rf after
- * form: 0, except RT_SOP_SHADE: 0 shade<false, false, false, false>, 1 shade<false, false, false, true>
+ *   RT_SOP_TRACE           plain_walk, walk_uv o, d, time, px, py, rf, UvSrc          hit, t, tif (t and tif 0 on a miss),
+ *                          (rt_plain_walk.h)                                       UvSrc after the walk (words 3..6:
+ *                                                                                  kind_idx, a, b, c), word 7 rf after
+ * RT_SOP_TRACE is ray_color's closest-hit walk over ray_t = [0.001, infinity): one lane per row runs the plain
+ * link walk (the context's plain link buffer, from global memory, from the root: no spine, collapse or pre-test
+ * nodes) and the generic leaf tests with media on -- the loop the first-hit pass runs with media cleared -- then
+ * hands the walk's uv over as after_trace() does.  A zero direction hits nothing and draws nothing.  The words
+ * are those of the oracle's op 8 (oracle/rt_oracle.h) except words 8..10, which stay 0 here: the oracle's
+ * visited-node count, leaf-slot count and visit hash describe the reference's stack walk, and the link walk's
+ * nodes differ from it by design (the same leaves in the same order).  Form 0: leaf_prims_t<false, false>
+ * under the context's box pre-test margin (option box_pretest on or off gives the same words); form 1:
+ * leaf_prims_t<false, true>, the shared-reciprocal divisions, RT_ERR_INVALID_ARG unless the scene is in that
+ * regime (rt_debug_last_launch out[2] of a render of it).  The link walk is acyclic, so it ends on any input.
+ * form: 0, except RT_SOP_TRACE (above) and RT_SOP_SHADE: 0 shade<false, false, false, false>, 1 shade<false, false, false, true>
  * (the per-pass trims of the compact-box kernels: the no-light mixture).  Form 1 gives form 0's words
  * but one: on a scene without lights, a row whose mixture draw is below 0.5 leaves rf one draw short of
  * form 0's (word 10 is one float32 addition of 0.001 less), because the trim leaves out lights_random,
@@ -102,7 +115,7 @@ int rt_debug_eval_op(int device, int op, int form, const void* recs, size_t rec_
  * device < 0: the guard alone (ctx may be NULL), nothing is launched and out is not written. */
 enum {
     RT_SOP_RAND = 0, RT_SOP_ONB, RT_SOP_UNIT_VEC, RT_SOP_MEDIUM_TAIL, RT_SOP_LIGHT_PDF, RT_SOP_LIGHT_DIR,
-    RT_SOP_CAMERA_RAY, RT_SOP_SHADE, RT_SOP_N
+    RT_SOP_CAMERA_RAY, RT_SOP_SHADE, RT_SOP_TRACE, RT_SOP_N
 };
 #define RT_SOP_ROW_F 20
 #define RT_SOP_OUT_W 12

@@ -273,7 +273,7 @@ def checker_parities(scales, p, which=0):
 # ---- the sampling, light, camera and shading operations on a scene (rt_debug.h's rt_debug_eval_shade_op
 # layout: RT_SOP_* numbers, rows of 20 floats, 12 output words)
 SHADE_OPS = {"rand": 0, "onb": 1, "unit_vec": 2, "medium_tail": 3, "light_pdf": 4, "light_dir": 5, "camera_ray": 6,
-             "shade": 7}
+             "shade": 7, "trace": 8}
 SOP_ROW_F, SOP_OUT_W = 20, 12
 # float index of each row field (ints as their bits)
 SOP_O, SOP_D, SOP_T, SOP_TIF, SOP_TIME, SOP_PX, SOP_PY, SOP_RF, SOP_ACC, SOP_UVK, SOP_UV, SOP_FRAME = \

@@ -78,6 +78,16 @@ struct TraceLog {
 };
 thread_local TraceLog* g_tlog = nullptr;
 
+// Optional per-walk record (oracle_eval_shade_op's RT_SOP_TRACE only; null while rendering): what one
+// trace_through_bvh visited and what its hits left behind.
+struct TraceInfo {
+    uint32_t nodes = 0, slots = 0, hash = ORACLE_VISIT_HASH_INIT;
+    int tif = 0;              // the closest hit's type | box face << 4 | index << 16
+    int face = 0;             // hit_box's side of the last box test
+    int uv_kind_idx = 0;      // the last accepted sphere / quad / box hit: who wrote hit_record.uv
+    float uv_a = 0, uv_b = 0, uv_c = 0;   // a sphere's rec.p; a quad's or box side's rec.uv
+};
+
 // ------------------------------------------------------- GLSL structs
 struct Ray { v3 o, dir; };
 struct HitRecord { bool is_front_face = false; v3 p = mk3s(0); v3 normal = mk3s(0); float t = 0; v2 uv = {0, 0}; };
@@ -93,6 +103,7 @@ struct Inv {
     v3 attenuation, color_from_emission;
     int material;
     int frame_count;
+    TraceInfo* T = nullptr;
 };
 
 // ---------------------------------------------------------- interval.glsl
@@ -423,7 +434,7 @@ bool hit_boundary(Inv& I, const Ray& ray, Interval ray_t, int idx, int type, Hit
             return hit_quad(ray, ray_t, S.quads[idx], rec);
         case RT_MODEL_BOX:
             if (I.C) { I.C->c.box_tests++; I.C->c.prim_bytes += 480; }
-            return hit_box(ray, ray_t, S.boxes[idx], rec);
+            return hit_box(ray, ray_t, S.boxes[idx], rec, I.T ? &I.T->face : nullptr);
         default: return false;
     }
 }
@@ -694,15 +705,28 @@ bool trace_through_bvh(Inv& I, const Ray& ray, Interval ray_t, HitRecord& rec) {
         const rt_bvh_node& node = S.nodes[node_idx];
         if (g_tlog) g_tlog->cur.push_back(node_idx);
         if (I.C) { I.C->c.node_visits++; I.C->c.node_bytes += 32; }
+        if (I.T) { I.T->nodes++; I.T->hash = ORACLE_VISIT_HASH_STEP(I.T->hash, (uint32_t)node_idx); }
         if (hit_aabb(ray, ray_t, node)) {
             int node_type = node.left_id & 0xFFFF;
             if (node_type != 0) {
                 if (g_tlog) g_tlog->cur.back() |= 0x40000000;   // log: leaf reached, its prims tested
                 int model_idx = (node.left_id >> 16) & 0xFFFF;
                 for (int i = 0; i < 2; i++) {
+                    if (I.T) I.T->slots++;
                     if (hit_model(I, ray, ray_t, model_idx, node_type, rec)) {
                         has_hit = true;
                         ray_t.max = rec.t;
+                        if (I.T) {
+                            TraceInfo& T = *I.T;
+                            T.tif = node_type | ((node_type == RT_MODEL_BOX ? T.face : 0) << 4) | (model_idx << 16);
+                            if (node_type == RT_MODEL_SPHERE) {
+                                T.uv_kind_idx = (1 << 16) | model_idx;
+                                T.uv_a = rec.p.x; T.uv_b = rec.p.y; T.uv_c = rec.p.z;
+                            } else if (node_type == RT_MODEL_QUAD || node_type == RT_MODEL_BOX) {
+                                T.uv_kind_idx = 2 << 16;
+                                T.uv_a = rec.uv.x; T.uv_b = rec.uv.y;
+                            }
+                        }
                         set_material_properties(I, model_idx, node_type, rec.p, rec.uv, rec.is_front_face);
                     }
                     model_idx = (node.right_id >> 16) & 0xFFFF;
@@ -1180,6 +1204,24 @@ int oracle_eval_shade_op(const oracle_scene_desc* d, int op, const float* rows, 
                 if (ended) put3(w + 1, fin);
                 else { put3(w + 1, ray.o); put3(w + 4, ray.dir); put3(w + 7, acc); }
                 w[10] = rt_f2u(I.rand_factor);
+                break;
+            }
+            case 8: {   // ray_color's walk: trace_through_bvh over [0.001, infinity)
+                TraceInfo T;
+                I.T = &T;
+                HitRecord rec;
+                const bool hit = trace_through_bvh(I, Ray{o, dd}, Interval{0.001f, RT_INFINITY}, rec);
+                w[0] = hit;
+                if (hit) { w[1] = rt_f2u(rec.t); w[2] = (uint32_t)T.tif; }
+                // hit_record.uv's source as the walk leaves it: unchanged when no sphere, quad or box side was
+                // accepted; a quad's source keeps the third word it had (only a sphere's point has one)
+                std::memcpy(w + 3, r + 15, 16);
+                if (T.uv_kind_idx != 0) {
+                    w[3] = (uint32_t)T.uv_kind_idx; w[4] = rt_f2u(T.uv_a); w[5] = rt_f2u(T.uv_b);
+                    if ((T.uv_kind_idx >> 16) == 1) w[6] = rt_f2u(T.uv_c);
+                }
+                w[7] = rt_f2u(I.rand_factor);
+                w[8] = T.nodes; w[9] = T.slots; w[10] = T.hash;
                 break;
             }
             default: return -1;

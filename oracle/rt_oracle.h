@@ -18,6 +18,8 @@
  * operations that choose a path's next direction and weight (oracle_eval_shade_op: rand as a float32
  * composition, transform_onb, rand_unit_vec, the medium's tail, light pdf and direction, the camera ray and
  * the shading step; tests/ref64_shade.py, tests/test_shade_ref64.py), draw counts included;
+ * and (f) the closest-hit walk that joins them (RT_SOP_TRACE below: trace_through_bvh itself; tests/ref64_trace.py,
+ * tests/test_trace_ref64.py) and the path loop replayed over those entry points (tests/path_replay.py);
  * everything else is "parity unpinned" against the reference itself.
  */
 #ifndef RT_ORACLE_H
@@ -111,9 +113,20 @@ int oracle_eval_op(int op, const void* recs, const float* rows, int n, int tex_f
  * output words per row) on scene d: rand, transform_onb, rand_unit_vec, the tail of hit_constant_medium
  * after its two boundary hits (medium_tail), lights_pdf_value, lights_random, main()'s time = rand() with
  * get_ray(), and the body of ray_color's loop after a trace that hit (shade_step, on the hit record and
- * material globals that hit leaves).  ray_color and hit_constant_medium call the same medium_tail and
- * shade_step.  Returns 0, or -1 for an unknown op or a shade row that names no record of the scene. */
+ * material globals that hit leaves), and ray_color's walk (trace_through_bvh, below).  ray_color and
+ * hit_constant_medium call the same medium_tail and shade_step.  Returns 0, or -1 for an unknown op or a shade row that names no record of the scene. */
 int oracle_eval_shade_op(const oracle_scene_desc* d, int op, const float* rows, int n, uint32_t* out);
+/* RT_SOP_TRACE (op 8) runs the trace_through_bvh that ray_color runs, over ray_t = [0.001, RT_INFINITY], on the
+ * row's o, d, time, px, py, rf and the uv source it had before the walk (row words 15..18).  Out words:
+ *   0 hit   1 t   2 tif (type | box face << 4 | index << 16; t and tif 0 on a miss)
+ *   3..6 the uv source after the walk (kind_idx, a, b, c) as rt_debug.h's UvSrc carries hit_record.uv: the
+ *        walk's last accepted sphere hit (1 << 16 | index, its rec.p) or quad / box side hit (2 << 16,
+ *        alpha, beta, c as it was), the input's when the walk accepted neither
+ *   7 rf after   8 nodes visited (popped)   9 leaf slots tested (hit_model calls)
+ *   10 the visited node indices' hash, in visit order: h = ORACLE_VISIT_HASH_INIT, then per node
+ *      h = ORACLE_VISIT_HASH_STEP(h, index) (FNV-1a over 32-bit words, modulo 2^32) */
+#define ORACLE_VISIT_HASH_INIT 2166136261u
+#define ORACLE_VISIT_HASH_STEP(h, node) ((((uint32_t)(h)) ^ ((uint32_t)(node))) * 16777619u)
 
 #ifdef __cplusplus
 }

@@ -149,7 +149,7 @@ int rt_debug_eval_op(int device, int op, int form, const void* recs, size_t rec_
 // records the scene holds), assembles the scene's argument block as rt_render does (scene_args) with
 // every LDS offset at -1, and binds the first device's copies; the device half is rt_shade_eval.hip.
 int rt_debug_eval_shade_op(rt_ctx* c, int device, int op, int form, const float* rows, int n, unsigned int* out) {
-    if (op < 0 || op >= RT_SOP_N || form < 0 || form > (op == RT_SOP_SHADE ? 1 : 0) || !rows || n < 0)
+    if (op < 0 || op >= RT_SOP_N || form < 0 || form > (op == RT_SOP_SHADE || op == RT_SOP_TRACE ? 1 : 0) || !rows || n < 0)
         return RT_ERR_INVALID_ARG;
     for (int i = 0; i < n; i++) {
         const float* r = rows + (size_t)i * RT_SOP_ROW_F;
@@ -185,12 +185,31 @@ int rt_debug_eval_shade_op(rt_ctx* c, int device, int op, int form, const float*
     rt_kernel_args a;
     if ((r = scene_args(*c, a, &c->err))) return r;
     clear_lds_tables(a, LDS_ALL);
+    if (op == RT_SOP_TRACE) {
+        // the plain walk's links (validate() built them) and its leaf tests: form 0 the generic ones under
+        // the context's box pre-test margin, form 1 the shared-reciprocal ones, only where the launch plan
+        // itself would take them
+        if (c->n_link_nodes > 0 && c->links.empty())
+            return set_err(c, RT_ERR_LIMIT, "rt_debug_eval_shade_op: the BVH has no link form (more than 65535 nodes)");
+        if (form == 1 && !a.fastdiv)
+            return set_err(c, RT_ERR_INVALID_ARG, "rt_debug_eval_shade_op: the scene is not in the shared-reciprocal regime");
+    }
     Device& d = c->devs[0];
     HIPCHK(c, hipSetDevice(d.id));
     HIPCHK(c, hipStreamSynchronize(d.stream));
     bind_scene(d, a);
     const int npad = (n + 63) / 64 * 64;
     Scratch d_rows, d_out, d_args;
+    if (op == RT_SOP_TRACE) {
+        Scratch d_links;
+        const bool ok = d_rows.upload_rows(rows, RT_SOP_ROW_F * sizeof(float), n, npad) &&
+                        d_out.alloc_zero((size_t)npad * RT_SOP_OUT_W * 4) && d_args.upload(&a, sizeof(a)) &&
+                        (c->links.empty() || d_links.upload(c->links.data(), c->links.size() * sizeof(float4))) &&
+                        !rt_launch_eval_trace_op((const rt_kernel_args*)d_args.p, form, d_links.p, c->n_link_nodes,
+                                                 (const float*)d_rows.p, d_out.p, npad, nullptr) &&
+                        d_out.download(out, (size_t)n * RT_SOP_OUT_W * 4);
+        return ok ? RT_OK : set_err(c, RT_ERR_DEVICE, "rt_debug_eval_shade_op: a HIP call failed");
+    }
     const bool ok = d_rows.upload_rows(rows, RT_SOP_ROW_F * sizeof(float), n, npad) &&
                     d_out.alloc_zero((size_t)npad * RT_SOP_OUT_W * 4) && d_args.upload(&a, sizeof(a)) &&
                     !rt_launch_eval_shade_op((const rt_kernel_args*)d_args.p, op, form, (const float*)d_rows.p, d_out.p,

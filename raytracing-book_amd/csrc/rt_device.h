@@ -268,3 +268,6 @@ int rt_launch_eval_op(const rt_kernel_args* dargs, int op, int form, const void*
 // (rt_debug.h rt_debug_eval_shade_op; rt_shade_eval.hip); n a multiple of 64
 int rt_launch_eval_shade_op(const rt_kernel_args* dargs, int op, int form, const float* drows, void* dout, int n,
                             void* stream);
+// ... and its RT_SOP_TRACE: the plain closest-hit walk (rt_plain_walk.h) over the plain link buffer dlinks
+int rt_launch_eval_trace_op(const rt_kernel_args* dargs, int form, const void* dlinks, int n_nodes, const float* drows,
+                            void* dout, int n, void* stream);

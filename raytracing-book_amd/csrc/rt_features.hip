@@ -11,7 +11,7 @@
 // order as whatever form the render's launch plan walks.  The argument block is the
 // pass's own: every LDS table off (-1), so the shared functions take their global-memory forms, and
 // no box pre-test (box_margin 0).  Leaf slots of type RT_MODEL_CONSTANT_MEDIUM are cleared before the
-// leaf tests, so no rand() is drawn anywhere.
+// leaf tests (plain_walk's MEDIA = false), so no rand() is drawn anywhere.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -22,6 +22,7 @@
 #include "rt_ctx.h"
 #include "rt_denoise.h"
 #include "rt_kernel_common.h"
+#include "rt_plain_walk.h"
 
 namespace {
 
@@ -42,34 +43,11 @@ __global__ void __launch_bounds__(256) features_kernel(const KP* __restrict__ Pp
     const v3 o = ld3(P.cam.camera_pos), d = sub3(pixel_base(P.cam, fx, fy), o);
     const float time = 0.0f;
 
-    // a new walk's set-up as rt_kernel.hip render_stream writes it out (its BEGIN block; kept in step by hand)
+    // the plain walk (rt_plain_walk.h) with media cleared: rf is never read (no medium is tested)
     Hit h;
-    h.t = 0.0f; h.tif = 0;
-    h.uv_kind_idx = 0; h.uv_a = 0.0f; h.uv_b = 0.0f;
-    bool has = false;
-    float tmax = RT_INFINITY, rf = 0.0f;   // rf: never read (no medium is tested)
-    const bool dir_zero = (d.x == 0.0f) && (d.y == 0.0f) && (d.z == 0.0f);   // hits nothing (bounce())
-    if (!dir_zero && n_nodes > 0) {
-        const v3 inv = mk3(1.0f / d.x, 1.0f / d.y, 1.0f / d.z);
-        const float a = g_dot(d, d);
-        const bool exact = (inv.x == -INFINITY) || (inv.y == -INFINITY) || (inv.z == -INFINITY);
-        const NodeSrc ns = {nullptr, reinterpret_cast<const char*>(links), 0u, nullptr};   // every node from global memory
-        const uint2* leaves = reinterpret_cast<const uint2*>(links + 2 * (size_t)n_nodes);
-        uint32_t nx = 0;
-        for (;;) {
-            nx = exact ? link_walk<true, false, true>(ns, nx, o, inv, 0.001f, tmax, nullptr)
-                       : link_walk<false, false, true>(ns, nx, o, inv, 0.001f, tmax, nullptr);
-            if (nx == RT_LINK_END) break;
-            const uint2 lf = ldg_u2(leaves + (nx & 0x7FFFFFFFu));
-            // the leaf's two type nibbles with a medium's cleared: an empty slot tests nothing
-            uint32_t ty = lf.x & 0xFFu;
-            if ((ty & 0xFu) == RT_MODEL_CONSTANT_MEDIUM) ty &= 0xF0u;
-            if ((ty >> 4) == RT_MODEL_CONSTANT_MEDIUM) ty &= 0x0Fu;
-            leaf_prims_t<false, false>(P, ty << 16, lf.y, o, d, inv, a, time, 0.001f, tmax, rf, fx, fy, h, has, nullptr);
-            nx = lf.x >> 8;   // the leaf's skip node
-            if (nx == RT_LINK_NEXT_END) break;
-        }
-    }
+    bool has;
+    float tmax, rf = 0.0f;
+    plain_walk<false, false>(P, links, n_nodes, o, d, time, rf, fx, fy, h, has, tmax);
     if (!has) {
         nd[px] = make_float4(0.0f, 0.0f, 0.0f, -1.0f);
         ai[px] = make_float4(P.background[0], P.background[1], P.background[2], __uint_as_float(RT_FEATURE_MISS));

@@ -6,6 +6,7 @@
 // the dynamic LDS and the launch has none.  Rows are processed in whole waves, in input order.
 #include "rt/rt_debug.h"
 #include "rt_kernel_common.h"
+#include "rt_plain_walk.h"
 
 namespace {
 
@@ -84,7 +85,51 @@ __global__ void __launch_bounds__(256) eval_shade_op_kernel(const KP* __restrict
     }
 }
 
+// RT_SOP_TRACE: the plain closest-hit walk from the root with media on, then the uv hand-over, as
+// render_stream's HIT block and after_trace() do them after a walk (h.t = tmax, walk_uv).  Words 8..10
+// (the oracle's visit counts and hash) stay 0: the link walk's nodes differ by design.
+template <bool FD>
+__global__ void __launch_bounds__(256) eval_trace_op_kernel(const KP* __restrict__ Pp, const float4* __restrict__ links,
+                                                            int n_nodes, const float* __restrict__ rows,
+                                                            uint32_t* __restrict__ out, int n) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;   // n is a multiple of 64: whole waves leave
+    const KP& P = *Pp;
+    const float* r = rows + (size_t)i * RT_SOP_ROW_F;
+    const v3 o = mk3(r[0], r[1], r[2]), d = mk3(r[3], r[4], r[5]);
+    const float time = r[8], px = r[9], py = r[10];
+    float rf = r[11];
+    UvSrc uvs = {__float_as_int(r[15]), r[16], r[17], r[18]};
+    Hit h;
+    bool has;
+    float tmax;
+    plain_walk<FD, true>(P, links, n_nodes, o, d, time, rf, px, py, h, has, tmax);
+    walk_uv(h, o, d, uvs);
+    uint32_t* w = out + (size_t)i * RT_SOP_OUT_W;
+    w[0] = has;
+    w[1] = __float_as_uint(has ? tmax : 0.0f);
+    w[2] = has ? (uint32_t)h.tif : 0u;
+    w[3] = (uint32_t)uvs.kind_idx;
+    w[4] = __float_as_uint(uvs.a);
+    w[5] = __float_as_uint(uvs.b);
+    w[6] = __float_as_uint(uvs.c);
+    w[7] = __float_as_uint(rf);
+}
+
 }  // namespace
+
+int rt_launch_eval_trace_op(const rt_kernel_args* dargs, int form, const void* dlinks, int n_nodes, const float* drows,
+                            void* dout, int n, void* stream) {
+    if (n <= 0) return 0;
+    if (n % 64) return -1;
+    if (form == 1)
+        hipLaunchKernelGGL(eval_trace_op_kernel<true>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, dargs,
+                           (const float4*)dlinks, n_nodes, drows, (uint32_t*)dout, n);
+    else
+        hipLaunchKernelGGL(eval_trace_op_kernel<false>, dim3((n + 255) / 256), dim3(256), 0, (hipStream_t)stream, dargs,
+                           (const float4*)dlinks, n_nodes, drows, (uint32_t*)dout, n);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 int rt_launch_eval_shade_op(const rt_kernel_args* dargs, int op, int form, const float* drows, void* dout, int n,
                             void* stream) {

@@ -333,21 +333,21 @@ def hit_box(boxes, rows):
     return dict(hit=has, t=t, face=face, alpha=al, beta=be, path=P)
 
 
-def hit_aabb(box6, rows):
-    """hit_aabb (hitting.glsl:55-76).  dict(hit, path).  In scope: finite slab values (a zero direction
-    component with the origin on its slab plane gives NaN: device against oracle only)."""
-    rows = np.asarray(rows, np.float32)
-    n = rows.shape[0]
-    P = Path(n)
-    bx = np.asarray(box6, np.float32).astype(np.float64).reshape(n, 6)
-    o, d = _vec(rows[:, 0:3]), _vec(rows[:, 3:6])
-    mn, mx = Err.of(rows[:, 6]), Err.of(rows[:, 7])
-    live = np.ones(n, bool)
+def _hit_aabb(P, live, o, d, bx, mn, mx):
+    """hit_aabb (hitting.glsl:55-76) on the box bx = [xmin, xmax, ymin, ymax, zmin, zmax] (Err each) over
+    ray_t = (mn, mx).  Returns the rows of `live` that hit."""
+    n = live.shape[0]
     for axis in range(3):                                     # :56
         with np.errstate(all="ignore"):
             adinv = Err(np.ones(n)) / d[axis]                 # :58
-            t0 = (Err(bx[:, 2 * axis]) - o[axis]) * adinv     # :60
-            t1 = (Err(bx[:, 2 * axis + 1]) - o[axis]) * adinv  # :61
+            t0 = (bx[2 * axis] - o[axis]) * adinv             # :60
+            t1 = (bx[2 * axis + 1] - o[axis]) * adinv         # :61
+            # 1 / +-0 is the same infinity in either precision, and a difference times it the same infinity
+            # too wherever the difference's sign is beyond its error: no bound to carry (inf * e is not one)
+            flat = np.isinf(adinv.v) & (adinv.e == 0.0)
+            for tt, plane in ((t0, bx[2 * axis]), (t1, bx[2 * axis + 1])):
+                diff = plane - o[axis]
+                tt.e = np.where(flat & (np.abs(diff.v) > diff.bound()), 0.0, tt.e)
         P.need(adinv, t0, t1, live=live, inf_ok=True)
         with np.errstate(invalid="ignore"):
             P.scope &= ~(live & (np.isnan(t0.e) | np.isnan(t1.e)))
@@ -358,7 +358,19 @@ def hit_aabb(box6, rows):
         miss, m = le(mx, mn)                                  # :71
         P.take(m, live)
         live = live & ~miss
-    return dict(hit=live, path=P)
+    return live
+
+
+def hit_aabb(box6, rows):
+    """hit_aabb (hitting.glsl:55-76).  dict(hit, path).  In scope: finite slab values (a zero direction
+    component with the origin on its slab plane gives NaN: device against oracle only)."""
+    rows = np.asarray(rows, np.float32)
+    n = rows.shape[0]
+    P = Path(n)
+    bx = np.asarray(box6, np.float32).astype(np.float64).reshape(n, 6)
+    hit = _hit_aabb(P, np.ones(n, bool), _vec(rows[:, 0:3]), _vec(rows[:, 3:6]), [Err(bx[:, k]) for k in range(6)],
+                    Err.of(rows[:, 6]), Err.of(rows[:, 7]))
+    return dict(hit=hit, path=P)
 
 
 # ------------------------------------------------------------------------------------------ texture.glsl

@@ -179,32 +179,40 @@ def onb(vec, normal):
 
 
 # ------------------------------------------------------------------------------------------ hitting.glsl
-def medium_tail(nid, t1, t2, a, tmin, tmax, seq):
-    """hit_constant_medium after its two boundary hits (hitting.glsl:172-187): a = dot(ray.dir, ray.dir)."""
-    nid, t1, t2, a, tmin, tmax = (Err.of(x) for x in (nid, t1, t2, a, tmin, tmax))
-    n = t1.v.shape[0]
-    P, D = Path(n), Draws(seq)
+def _medium_tail(P, draw, live, nid, t1, t2, a, tmin, tmax):
+    """hit_constant_medium after its two boundary hits (hitting.glsl:172-187) for the rows `live`; draw(rows)
+    gives those rows their next rand().  Returns (hit, t)."""
+    n = live.shape[0]
     c, m = lt(t1, tmin)                                                   # :172
-    P.take(m)
+    P.take(m, live)
     t1 = pick(c, tmin, t1)
     c, m = lt(tmax, t2)                                                   # :173
-    P.take(m)
+    P.take(m, live)
     t2 = pick(c, tmax, t2)
     ge, m = le(t2, t1)                                                    # :175
-    P.take(m)
-    live = ~ge
+    P.take(m, live)
+    live = live & ~ge
     c, m = lt(t1, Err(np.zeros(n)))                                       # :178
     P.take(m, live)
     t1 = pick(c & live, Err(np.zeros(n)), t1)
     length = a.sqrt()                                                     # :181
     inside = (t2 - t1) * length                                           # :182
-    hd = nid * _log(D.take(live))                                         # :183
+    hd = nid * _log(draw(live))                                           # :183
     P.need(hd, inside, live=live, inf_ok=True)
     past, m = lt(inside, hd)                                              # :185
     P.take(m, live)
     hit = live & ~past
     t = t1 + hd / length                                                  # :188
     P.need(t, live=hit)
+    return hit, t
+
+
+def medium_tail(nid, t1, t2, a, tmin, tmax, seq):
+    """hit_constant_medium after its two boundary hits (hitting.glsl:172-187): a = dot(ray.dir, ray.dir)."""
+    nid, t1, t2, a, tmin, tmax = (Err.of(x) for x in (nid, t1, t2, a, tmin, tmax))
+    n = t1.v.shape[0]
+    P, D = Path(n), Draws(seq)
+    hit, t = _medium_tail(P, D.take, np.ones(n, bool), nid, t1, t2, a, tmin, tmax)
     return dict(cls=dict(hit=hit, count=D.k), val=dict(t=t), mask=dict(t=hit), path=P)
 
 

@@ -133,17 +133,20 @@ def test_the_hook_refuses_rows_outside_its_guard():
     from rtamd._lib import debug_eval_shade_op
     ok = pyoracle.shade_rows(3, px=[0, 16383, 5], py=[0, 8191, 16383], rf=[0, 4095.5, 1])
     ok[:, 0:9] = np.nan   # the other fields are free
-    for op in range(8):
+    for op in range(9):
         debug_eval_shade_op(None, op, 0, ok, device=-1)
     for col, bad in ((9, np.nan), (9, np.inf), (9, -1.0), (9, 16384.0), (10, np.nan), (10, -0.5), (10, 16384.0),
                      (11, np.nan), (11, np.inf), (11, -0.001), (11, 4096.0)):
         rows = ok.copy()
         rows[1, col] = bad
-        for op in (0, 2, 6, 7):
+        for op in (0, 2, 6, 7, 8):
             with pytest.raises(rtamd.RTError):
                 debug_eval_shade_op(None, op, 0, rows, device=-1)
     with pytest.raises(rtamd.RTError):
         debug_eval_shade_op(None, 7, 2, ok, device=-1)   # shade has forms 0 and 1
+    debug_eval_shade_op(None, 8, 1, ok, device=-1)       # ... and so has the walk (the scene decides whether 1 may run)
+    with pytest.raises(rtamd.RTError):
+        debug_eval_shade_op(None, 8, 2, ok, device=-1)
     with pytest.raises(rtamd.RTError):
         debug_eval_shade_op(None, 2, 1, ok, device=-1)
 
