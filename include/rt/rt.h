@@ -388,6 +388,91 @@ int rt_denoise_guided_host(const float* image, const float* m2, const int32_t* t
                            const float* normal_depth, const float* albedo_id, int width, int height,
                            const rt_denoise_params* params, const rt_guide_params* guides, float* rgba_out);
 
+/* ---- Temporal reprojection: the accumulated image carried into the new view after a camera move ----
+ * rt_set_camera restarts the running mean at frame 1.  rt_history_capture keeps what the old view had
+ * learned -- per pixel (r, g, b, n), n the frames behind that mean, with the first-hit buffers and the
+ * camera they were made with -- and rt_reproject, after the move, gathers it into the new view wherever
+ * the new view's first hit is a surface the old view saw, and blends it with the new view's own few
+ * frames by their counts.  It writes a buffer of its own, (r, g, b, n_out) per pixel: image, moments, tile
+ * counts, features and the denoised buffer keep their bits, and a context that never calls these
+ * allocates and runs nothing new.  Single-device contexts without rt_set_partition (RT_ERR_STATE).
+ *
+ * The history view's matrix.  With the history camera's c0 = pixel_delta_u, c1 = pixel_delta_v,
+ * c2 = up_left - camera_pos, all in double (a x b = (a.y*b.z - a.z*b.y, a.z*b.x - a.x*b.z,
+ * a.x*b.y - a.y*b.x), a . b = (a.x*b.x + a.y*b.y) + a.z*b.z, no contraction):
+ *   det = c0 . (c1 x c2);   rows of M: (c1 x c2) / det, (c2 x c0) / det, (c0 x c1) / det,
+ * each entry rounded to f32 once.  det 0 or not finite: RT_ERR_INVALID_ARG.  M takes a point's offset
+ * from the history camera to (a, b, c) with a / c, b / c its pixel coordinates in the history view.
+ *
+ * The definition.  All arithmetic below is f32 without contraction, using only + - * / fabsf floorf,
+ * rt_glsl.h's g_max / g_min (g_min(a, b) = b < a ? b : a) and comparisons, so a float32 restatement matches
+ * bit for bit.  pixel_base(cam, fx, fy).c = (up_left.c + pixel_delta_u.c * fx) + pixel_delta_v.c * fy
+ * (rt_render_features' coord); dot(a, b) = (a.x*b.x + a.y*b.y) + a.z*b.z.  finite(v): fabsf(v) <= FLT_MAX.
+ * For the current pixel p = (x, y) of a W x H image: C = the image's rgb; n_c = (float) of its 8x8 tile's
+ * frame count, taken as 0 when a component of C is not finite; (N, t) and (A, id) its first-hit words;
+ * o, o_h the current and the history camera_pos.
+ *   1. If p is a miss (id == RT_FEATURE_MISS) or not guide-good (rt_denoise_guided: N, t, A all finite),
+ *      there is no reprojection.
+ *   2. d = pixel_base(cam, (float)x, (float)y) - o;   P.c = o.c + d.c * t.
+ *   3. w = P - o_h;   a = (M00*w.x + M01*w.y) + M02*w.z,  b and c likewise from rows 1 and 2.
+ *      Reject unless c > 0.   fx = a / c, fy = b / c.   Reject unless fx > -1 && fx < (float)W &&
+ *      fy > -1 && fy < (float)H (a NaN fails).   x0 = floorf(fx), ax = fx - x0;  y0, ay likewise.
+ *   4. Four taps q = (x0 + i, y0 + j), j outer over {0, 1}, i inner over {0, 1}, each with weight
+ *      u = (i ? ax : 1 - ax) * (j ? ay : 1 - ay).  A tap is accepted when q is inside the image, the
+ *      history's n_h(q) > 0, q's history features are guide-good and a hit, its id word equals p's (the
+ *      same primitive and box face), (N.x*Nh.x + N.y*Nh.y) + N.z*Nh.z >= cos_min, and, unless kz == 0,
+ *        d_q = pixel_base(cam_h, (float)q.x, (float)q.y) - o_h,   t_exp = dot(w, d_q) / dot(d_q, d_q),
+ *        fabsf(t_exp - t_h(q)) <= kz * t_exp.
+ *      A skipped tap is read at the clamped position and leaves the sums untouched.  The sums start at
+ *      +0:   sw = sw + u;   sc.c = sc.c + u * H(q).c  for c in r, g, b;   sn = sn + u * n_h(q).
+ *   5. Reject unless sw > 0.   Hc.c = sc.c / sw;   n_hist = g_min(sn / sw, max_history).
+ *   6. Output: rejected or not reprojected: (C, n_c);  else if n_c == 0: (Hc, n_hist);  else
+ *      n_out = n_c + n_hist,  alpha = n_hist / n_out,  out.c = C.c + alpha * (Hc.c - C.c),  (out, n_out).
+ * csrc/rt_reproject_math.h holds these operations once, for the kernel and for rt_reproject_host.
+ * The primitives are convex, so a ray meets one at most once from outside: equal ids at p and q mean
+ * the history sample lies on the surface p sees, and the id test is the disocclusion test.
+ *
+ * cos_min is in [-1, 1], kz >= 0 and finite (0 switches the depth test off), max_history > 0 and
+ * finite, reserved 0 (RT_ERR_INVALID_ARG otherwise); NULL = the defaults below, the best setting of
+ * tools/reproject_quality.py's grid on scene 6 after a sideways move (among equal ratios the strictest;
+ * profiles/reproject_quality.json).  max_history bounds how long a view-dependent surface (metal, glass)
+ * keeps showing what the old view saw in it: history is shaded for the old camera. */
+#define RT_REPROJECT_DEFAULT_COS_MIN 0.9f
+#define RT_REPROJECT_DEFAULT_KZ 0.1f
+#define RT_REPROJECT_DEFAULT_MAX_HISTORY 64.0f
+enum { RT_HISTORY_FROM_IMAGE = 0, RT_HISTORY_FROM_REPROJECTED = 1 };
+typedef struct rt_reproject_params { float cos_min, kz, max_history; int reserved[5]; /* must be 0 */ } rt_reproject_params;
+
+/* Keep the history: device-to-device copies on the context's stream into buffers the context owns
+ * (48 bytes per pixel, allocated by the first call), and the current camera block with its M.
+ * RT_HISTORY_FROM_IMAGE: (r, g, b, n) from the image, n = (float) of the pixel's tile frame count, 0 where
+ * a component of rgb is not finite; needs an image, rt_set_moments(ctx, 1) with tile counts that are not
+ * all 0 (a render from frame 1; a single tile whose count is 0 gives n = 0) and feature buffers held and
+ * not stale (rt_render_features), RT_ERR_STATE naming what is lacking.  RT_HISTORY_FROM_REPROJECTED: the last
+ * rt_reproject result's (r, g, b, n_out) with the current feature buffers -- history that survives a camera
+ * that keeps moving with a frame or two per pose; RT_ERR_STATE if no result is held or the features
+ * are stale.  RT_ERR_INVALID_ARG: another source, or a camera whose det is 0 or not finite.
+ * The history is held until rt_resize, rt_destroy, or rt_upload_buffer / rt_upload_texture (the ids
+ * no longer mean the same surfaces); it survives rt_set_camera, rt_set_params, rt_set_bvh_mode and
+ * later renders. */
+int rt_history_capture(rt_ctx* ctx, int source);
+/* Queue the gather (one kernel) on the context's stream behind the queued renders.  Needs, RT_ERR_STATE
+ * naming what is lacking otherwise: history held (rt_history_capture), the image's size equal to the
+ * history's, rt_set_moments(ctx, 1), and feature buffers held and current for the current camera
+ * (rt_render_features).  A tile whose count is 0 has n_c = 0.  The result is held until the next
+ * rt_reproject, rt_resize or rt_destroy. */
+int rt_reproject(rt_ctx* ctx, const rt_reproject_params* params);
+/* rt_sync, then the result as W*H*4 floats (r, g, b, n_out); RT_ERR_STATE with no result held. */
+int rt_read_reprojected(rt_ctx* ctx, float* rgbn);
+/* Host only, no device: the same header's arithmetic over caller arrays.  history_rgbn, history_nd,
+ * history_ai, image, normal_depth, albedo_id: W*H*4 floats each; the two 28-float camera blocks;
+ * tile_frames: one count >= 0 per 8x8 tile of the current image, row-major, n_tiles = ceil(W/8) * ceil(H/8)
+ * (RT_ERR_INVALID_ARG otherwise, and for bad params or a singular history camera). */
+int rt_reproject_host(const float* history_rgbn, const float* history_nd, const float* history_ai,
+                      const float history_camera[28], const float* image, const int32_t* tile_frames, int n_tiles,
+                      const float* normal_depth, const float* albedo_id, const float camera[28], int width, int height,
+                      const rt_reproject_params* params, float* rgbn_out);
+
 /* Per-frame u_rand_factor for frame index f (0-based) of a seeded render:
  * top 24 bits of splitmix64(seed, f) / 2^24, in [0,1).  Stands in for the
  * reference's (float)Math.random() per frame (RaytraceExecutor.java:124). */

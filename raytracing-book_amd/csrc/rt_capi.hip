@@ -20,6 +20,7 @@
 #include "rt_ctx.h"
 #include "rt_denoise.h"
 #include "rt_plan.h"
+#include "rt_reproject.h"
 
 using namespace rt_impl;
 
@@ -120,6 +121,7 @@ int rt_destroy(rt_ctx* c) {
         dev_free(d.m2); dev_free(d.tile_sums); dev_free(d.node_hits); dev_free(d.tile_list);
         dev_free(d.dn_px[0]); dev_free(d.dn_px[1]); dev_free(d.dn_vb); dev_free(d.dn_counts);
         dev_free(d.ft_nd); dev_free(d.ft_ai); dev_free(d.ft_links); dev_free(d.ft_args);
+        dev_free(d.hs_px); dev_free(d.hs_nd); dev_free(d.hs_ai); dev_free(d.rp_out); dev_free(d.rp_counts);
         comm_destroy(d);
         if (d.ring) (void)hipHostFree(d.ring);
         for (auto& e : d.ring_ev)
@@ -141,6 +143,7 @@ int rt_upload_buffer(rt_ctx* c, int binding, const void* bytes, size_t nbytes) {
     int r = prep_buffer(*c, binding, bytes, nbytes, p, &c->err);
     if (r) return r;
     c->ft_valid = c->ft_links_ok = false;   // the first-hit buffers are another scene's now
+    history_drop(c);                        // ... and the history's ids no longer mean the same surfaces
     for (Device& d : c->devs) {
         DevBuf* b = nullptr;
         switch (binding) {
@@ -172,6 +175,7 @@ int rt_upload_texture(rt_ctx* c, int slot, int format, int w, int h, const void*
     int r = prep_texture(slot, format, w, h, texels, p, &c->err);
     if (r) return r;
     c->ft_valid = false;   // the first-hit albedo was another texture's
+    history_drop(c);       // ... and so was what the history had accumulated
     for (Device& d : c->devs) {
         r = dev_alloc_copy(c, d, d.tex[slot], p.src, p.bytes);
         if (r) return r;
@@ -229,6 +233,7 @@ int rt_resize(rt_ctx* c, int w, int h) {
     c->staged_frames = 0;
     denoise_free(c);        // (alloc_image left every stream idle) the filtered image was the old size's
     features_free(c);       // ... and so were the first-hit buffers
+    reproject_free(c);      // ... the history and the reprojected result
     set_all_frames(c, 0);   // another image: no tile holds a frame, and a tile mask no longer fits it
     c->mask_set = false;
     c->act_list.clear();

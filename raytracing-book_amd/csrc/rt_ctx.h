@@ -1,5 +1,5 @@
 // rt_ctx.h — the context behind the C ABI's rt_ctx handle and the device helpers its
-// translation units share (rt_capi.hip, rt_comm.hip, rt_debug.hip, rt_denoise.hip, rt_features.hip).  Internal to the libraries.
+// translation units share (rt_capi.hip, rt_comm.hip, rt_debug.hip, rt_denoise.hip, rt_features.hip, rt_reproject.hip).  Internal to the libraries.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -53,6 +53,9 @@ struct Device {
     DevBuf ft_nd, ft_ai;     // rt_render_features: normal_depth and albedo_id, float4 [local_rows][W] each (rt_features.hip) ...
     DevBuf ft_links;         // ... the pass's plain link buffer (SceneState::links) ...
     DevBuf ft_args;          // ... and its own rt_kernel_args (no LDS tables; rt_ctx::ft_args_host holds the same)
+    DevBuf hs_px, hs_nd, hs_ai;   // rt_history_capture: the history's {r, g, b, n} and first-hit buffers, float4 [local_rows][W] each (rt_reproject.hip) ...
+    DevBuf rp_out;           // ... rt_reproject's result {r, g, b, n_out} ...
+    DevBuf rp_counts;        // ... and its copy of the per-tile frame counts (int32, rt_ctx::rp_counts holds the same)
     DevBuf wbuf;             // pooled units (ordered / one chunk): per resident wave 64 x chunk_frames colours
     DevBuf finfo;            // exact near-first walk tables (variant 61)
     DevBuf f2inner, f2leaves;
@@ -94,6 +97,14 @@ struct rt_ctx : rt_impl::SceneState {
     // current tree's links (cleared with ft_valid); the argument block last copied to Device::ft_args
     bool ft_valid = false, ft_links_ok = false;
     std::vector<uint8_t> ft_args_host;
+    // rt_history_capture: a history is held (Device::hs_*), of this size, made with this camera block,
+    // whose matrix M is hs_M (rt.h); rt_reproject: a result is held (Device::rp_out), and the per-tile
+    // counts last copied to Device::rp_counts (copied again only when they change)
+    bool hs_valid = false, rp_valid = false;
+    int hs_w = 0, hs_h = 0;
+    rt_camera_ubo hs_cam{};
+    float hs_M[9] = {0};
+    std::vector<int32_t> rp_counts;
     // the first device's staged colours of the last launch (rt_debug_read_samples): frames, sparse flags
     int staged_frames = 0;
     bool staged_sparse = false;

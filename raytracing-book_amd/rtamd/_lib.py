@@ -89,6 +89,12 @@ class RtGuideParams(ctypes.Structure):
     _fields_ = [("kn", ctypes.c_float), ("kz", ctypes.c_float), ("ka", ctypes.c_float), ("reserved", ctypes.c_int * 5)]
 
 
+class RtReprojectParams(ctypes.Structure):
+    """rt.h rt_reproject_params."""
+    _fields_ = [("cos_min", ctypes.c_float), ("kz", ctypes.c_float), ("max_history", ctypes.c_float),
+                ("reserved", ctypes.c_int * 5)]
+
+
 RT_FEATURE_MISS = 0xFFFFFFFF   # rt.h
 
 RT_PK_N = 33   # rt_debug.h RT_PK_N
@@ -152,6 +158,13 @@ def _amd_protos(L, old_rev=False):
         _proto(L, "rt_denoise_guided", i, vp, dp_p, gp_p)
         _proto(L, "rt_denoise_guided_host", i, c_float_p, c_float_p, i32_p, i, c_float_p, c_float_p, i, i, dp_p, gp_p,
                c_float_p)
+    if not old_rev or hasattr(L, "rt_reproject"):   # ... or from before the temporal reprojection
+        rp_p, i32_p = ctypes.POINTER(RtReprojectParams), ctypes.POINTER(ctypes.c_int32)
+        _proto(L, "rt_history_capture", i, vp, i)
+        _proto(L, "rt_reproject", i, vp, rp_p)
+        _proto(L, "rt_read_reprojected", i, vp, c_float_p)
+        _proto(L, "rt_reproject_host", i, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, i32_p, i, c_float_p,
+               c_float_p, c_float_p, i, i, rp_p, c_float_p)
     _proto(L, "rt_abi_version", i)
     _proto(L, "rt_create", i, i, c_int_p, ctypes.POINTER(vp))
     _proto(L, "rt_destroy", i, vp)

@@ -310,6 +310,65 @@ def pack_albedo_id(albedo, ids):
     return out
 
 
+REPROJECT_DEFAULTS = (0.9, 0.1, 64.0)   # rt.h RT_REPROJECT_DEFAULT_*: cos_min, kz, max_history
+HISTORY_SOURCES = {"image": 0, "reprojected": 1}   # rt.h RT_HISTORY_FROM_*
+
+
+def _reproject_params(cos_min, kz, max_history):
+    """rt_reproject_params for (cos_min, kz, max_history); None for all three = NULL (the library's defaults)."""
+    if cos_min is None and kz is None and max_history is None:
+        return None
+    p = _lib.RtReprojectParams()
+    p.cos_min = REPROJECT_DEFAULTS[0] if cos_min is None else float(cos_min)
+    p.kz = REPROJECT_DEFAULTS[1] if kz is None else float(kz)
+    p.max_history = REPROJECT_DEFAULTS[2] if max_history is None else float(max_history)
+    return ctypes.byref(p)
+
+
+def history_from_image(image, tile_frames):
+    """What rt_history_capture keeps of an [H, W, 4] image and one frame count per 8x8 tile (row-major; a
+    scalar stands for every tile): [H, W, 4] float32 (r, g, b, n), n = 0 where a component of rgb is not finite."""
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    H, W = img.shape[:2]
+    tx, ty = (W + 7) // 8, (H + 7) // 8
+    tf = np.ascontiguousarray(tile_frames, dtype=np.int32).ravel()
+    if tf.size == 1:
+        tf = np.full(tx * ty, tf[0], np.int32)
+    n = np.repeat(np.repeat(tf.reshape(ty, tx), 8, axis=0), 8, axis=1)[:H, :W].astype(np.float32)
+    out = img.copy()
+    out[..., 3] = np.where(np.isfinite(img[..., :3]).all(axis=-1), n, np.float32(0.0))
+    return out
+
+
+def reproject_host(history, history_nd, history_ai, history_camera, image, tile_frames, normal_depth, albedo_id, camera,
+                   cos_min=None, kz=None, max_history=None, lib=None):
+    """rt_reproject_host (host only, no device): the history (r, g, b, n), its first-hit buffers and 28-float
+    camera block; the current image, one frame count per 8x8 tile (row-major; a scalar stands for every tile),
+    first-hit buffers and camera block -> [H, W, 4] float32 (r, g, b, n_out).  All buffers are [H, W, 4]."""
+    L = lib or _lib.amd()
+    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (history, history_nd, history_ai, image, normal_depth, albedo_id)]
+    img = arrs[3]
+    if img.ndim != 3 or img.shape[2] != 4 or any(a.shape != img.shape for a in arrs):
+        raise ValueError("history, image and the first-hit buffers are [H, W, 4]")
+    cams = [np.ascontiguousarray(c, dtype=np.float32).ravel() for c in (history_camera, camera)]
+    if any(c.size != 28 for c in cams):
+        raise ValueError("a camera block is 28 floats")
+    H, W = img.shape[:2]
+    nt = ((W + 7) // 8) * ((H + 7) // 8)
+    tf = np.ascontiguousarray(tile_frames, dtype=np.int32).ravel()
+    if tf.size == 1:
+        tf = np.full(nt, tf[0], np.int32)
+    out = np.empty_like(img)
+    fp = lambda a: a.ctypes.data_as(c_float_p)  # noqa: E731
+    rc = L.rt_reproject_host(fp(arrs[0]), fp(arrs[1]), fp(arrs[2]), fp(cams[0]), fp(img),
+                             tf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(tf.size), fp(arrs[4]), fp(arrs[5]),
+                             fp(cams[1]), W, H, _reproject_params(cos_min, kz, max_history), fp(out))
+    if rc != 0:
+        raise RTError(rc, "rt_reproject_host: cos_min in [-1, 1], kz >= 0, max_history > 0, one count >= 0 per 8x8 tile "
+                          "and a history camera with independent pixel deltas and view corner required")
+    return out
+
+
 SHAPES = {0: "fast-lds", 1: "fast-global", 2: "link-lds", 3: "meta-lds", 4: "meta-global", 5: "link-two-level"}
 
 
@@ -583,6 +642,24 @@ class RenderContext:
         N = 0, t = -1, the background colour and id RT_FEATURE_MISS."""
         nd, ai = self.read_features_raw()
         return nd, np.ascontiguousarray(ai[..., :3]), np.ascontiguousarray(ai.view(np.uint32)[..., 3])
+
+    # -- temporal reprojection (rt.h rt_history_capture / rt_reproject)
+    def history_capture(self, source="image"):
+        """rt_history_capture: keep (r, g, b, n), the first-hit buffers and the camera as the history, from the
+        image ("image": needs set_moments() and render_features()) or from the last reproject() result
+        ("reprojected")."""
+        self._check(self._L.rt_history_capture(self._h, HISTORY_SOURCES[source] if isinstance(source, str) else int(source)))
+
+    def reproject(self, cos_min=None, kz=None, max_history=None):
+        """rt_reproject: queue the gather of the history into the current view (after the camera move, the new
+        view's render and render_features()).  Image, moments, counts and features are left as they are."""
+        self._check(self._L.rt_reproject(self._h, _reproject_params(cos_min, kz, max_history)))
+
+    def read_reprojected(self):
+        """rt_read_reprojected: the result as [H, W, 4] float32 (r, g, b, n_out)."""
+        out = np.empty((self.local_rows, self.width, 4), dtype=np.float32)
+        self._check(self._L.rt_read_reprojected(self._h, out.ctypes.data_as(c_float_p)))
+        return out
 
     def read_samples(self):
         """rt_debug_read_samples: the last launch's staged colours, [n_frames, local_rows, W, 4]."""
