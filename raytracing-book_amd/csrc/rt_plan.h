@@ -37,7 +37,10 @@
 // RT_OPT_STD forms of the division kernels.  Every entry also has its twin for a launch under a tile
 // mask (OPT | RT_OPT_MASK), and in the A/B library its stats twin (STATS, OPT without RT_OPT_BOXQ).
 // rt_kernel.hip instantiates and dispatches from this list; plan_kernel chooses only from it
-// (tests/test_launch_plan.py: every entry is reachable and nothing else is chosen).
+// (tests/test_launch_plan.py: some input of plan_kernel chooses each entry, and nothing else is chosen).
+// rt_render reaches all but four: the two-level kernels with RT_OPT_STD and their mask twins, since
+// plan_lds stages no shading table for a two-level walk and std_cfg needs tex_lds
+// (tests/test_kernel_matrix.py; tests/test_gpu_kernel_matrix.py launches the other 52).
 #define RT_RENDER_KERNELS_LDS(X, BLOCK)                                                          \
     X(BLOCK, RT_OPT_SM_STREAM)                                                                   \
     X(BLOCK, RT_OPT_SM_STREAM | RT_OPT_BOXC)                                                     \
