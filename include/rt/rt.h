@@ -473,6 +473,73 @@ int rt_reproject_host(const float* history_rgbn, const float* history_nd, const 
                       const float* normal_depth, const float* albedo_id, const float camera[28], int width, int height,
                       const rt_reproject_params* params, float* rgbn_out);
 
+/* ---- Sample variance carried through reprojection, and the preview filter over the moved view ------
+ * After a move rt_reproject's result is an n-frame picture where the old view saw the surface and a 1- or
+ * 2-frame picture elsewhere (disoccluded strips, the background, rejected taps).  With
+ * rt_set_history_variance(ctx, 1) a per-sample variance s2 of y = (r + g) + b travels with the history
+ * and with the result, and rt_denoise_reprojected runs rt_denoise's levels over the result.  A negative
+ * s2 means "unknown"; every "known" test is written s2 >= 0, so a NaN is unknown.  Carrying the variance
+ * of one sample, not of the mean, makes its blend a colour channel's: for out = (n_c C + n_h Hc) / n_out
+ * the variance of out is (n_c s2_c + n_h s2_h) / n_out^2, so s2_out is the count-weighted mean of s2_c and
+ * s2_h and the variance of the mean is s2_out / n_out.  All arithmetic is f32 without contraction, every
+ * step one operation in the order written, with only + - * / fabsf sqrtf floorf g_max g_min and
+ * comparisons.
+ *
+ *   history_s2(C, M2.w, count): n = (float)count, 0 where a component of C is not finite;
+ *     n >= 2 and finite(M2.w): g_max(0, M2.w / (n - 1.0f));   otherwise -1.
+ *   rt_history_capture keeps, beside (r, g, b, n), history_s2 of the image (RT_HISTORY_FROM_IMAGE) or a
+ *   copy of the result's s2 (RT_HISTORY_FROM_REPROJECTED).
+ *   rt_reproject, in step 4 with `use` the tap's acceptance and s = s2_h(q) read at the same clamped
+ *   position:   kn = use && s >= 0;   ss = kn ? ss + u * s : ss;   sws = kn ? sws + u : sws   (both start
+ *   at +0), and after the taps s2_hist = sws > 0 ? ss / sws : -1.   With s2_c = history_s2(C, M2.w(p),
+ *   count), the result's s2 is: s2_c wherever step 6 gives (C, n_c);  s2_hist where n_c == 0;  otherwise
+ *   s2_hist if !(s2_c >= 0), else s2_c if !(s2_hist >= 0), else s2_c + alpha * (s2_hist - s2_c) with step
+ *   6's alpha.  The (r, g, b, n_out) word is rt_reproject's, bit for bit.
+ *
+ * Off is the default: history, kernels, buffers and launches are as described above and nothing new is
+ * allocated.  Changing the value drops the history and the result (RT_ERR_STATE from their readers until
+ * the next rt_history_capture / rt_reproject).  On, the history and the result hold 4 more bytes per pixel. */
+int rt_set_history_variance(rt_ctx* ctx, int on);
+/* rt_sync, then the result's s2 as W*H floats; RT_ERR_STATE when no result with variance is held. */
+int rt_read_reprojected_variance(rt_ctx* ctx, float* s2);
+
+/* rt_denoise_guided's levels over the reprojected view.  Level 0 at pixel p with R = (r, g, b, n) the
+ * result word, s2 its variance and id the id word of the albedo_id buffer:
+ *   bad (V = -1, passes through unchanged, never a tap): !(finite(y(R)) && n > 0);
+ *   s2 >= 0 && finite(s2):  V_0 = s2 / n;
+ *   otherwise the spatial estimate (the fallback for a pixel with no usable sample variance): taps
+ *   (dy, dx) in {-2..2}^2 at spacing 1, row-major (dy outer), the centre included; a tap is accepted when it
+ *   lies in the image, is not bad and its id word equals p's (two misses are equal); a skipped tap is read
+ *   at the clamped position and leaves the sums untouched.  Pass 1:  cnt = cnt + 1.0f;  sy = sy + y(q);
+ *   then m = sy / cnt.  Pass 2 over the same taps:  e = y(q) - m;  sd = sd + e * e.
+ *   V_0 = +0 if cnt < 2, else (sd / (cnt - 1.0f)) / n.
+ * C_0 = R's rgb; levels 0 .. levels-1 then run exactly as in rt_denoise / rt_denoise_guided over the current
+ * feature buffers.  params and guides mean what they mean in rt_denoise_guided: NULL = the defaults, all-zero
+ * strengths = the unguided filter.  There is no minimum frame count.  The spatial estimate understates the
+ * variance at the border between fresh and well-sampled pixels (the well-sampled neighbours of one id pull
+ * the spread down), which errs towards less blur.  The result is read with rt_read_denoised and held under
+ * rt_denoise's rules; image, moments, counts, features, history and the reprojected result keep their bits.
+ * RT_ERR_STATE naming what is lacking: no reprojected result with variance held, feature buffers not
+ * current, feature buffers rendered again since that rt_reproject, a multi-device context or one under
+ * rt_set_partition. */
+int rt_denoise_reprojected(rt_ctx* ctx, const rt_denoise_params* params, const rt_guide_params* guides);
+
+/* Host only, no device: history_s2 per pixel -> s2_out (W*H floats); image / m2 W*H*4 floats, tile_frames
+ * one count >= 0 per 8x8 tile (RT_ERR_INVALID_ARG otherwise, as rt_reproject_host). */
+int rt_history_variance_host(const float* image, const float* m2, const int32_t* tile_frames, int n_tiles,
+                             int width, int height, float* s2_out);
+/* rt_reproject_host with the variance: history_s2 W*H floats, m2 the current view's W*H*4 moments;
+ * rgbn_out is rt_reproject_host's bit for bit, s2_out W*H floats. */
+int rt_reproject_variance_host(const float* history_rgbn, const float* history_nd, const float* history_ai,
+                               const float* history_s2, const float history_camera[28], const float* image,
+                               const float* m2, const int32_t* tile_frames, int n_tiles, const float* normal_depth,
+                               const float* albedo_id, const float camera[28], int width, int height,
+                               const rt_reproject_params* params, float* rgbn_out, float* s2_out);
+/* rt_denoise_reprojected over caller arrays: rgbn, normal_depth, albedo_id W*H*4 floats, s2 W*H floats. */
+int rt_denoise_reprojected_host(const float* rgbn, const float* s2, const float* normal_depth, const float* albedo_id,
+                                int width, int height, const rt_denoise_params* params, const rt_guide_params* guides,
+                                float* rgba_out);
+
 /* Per-frame u_rand_factor for frame index f (0-based) of a seeded render:
  * top 24 bits of splitmix64(seed, f) / 2^24, in [0,1).  Stands in for the
  * reference's (float)Math.random() per frame (RaytraceExecutor.java:124). */

@@ -56,6 +56,7 @@ struct Device {
     DevBuf hs_px, hs_nd, hs_ai;   // rt_history_capture: the history's {r, g, b, n} and first-hit buffers, float4 [local_rows][W] each (rt_reproject.hip) ...
     DevBuf rp_out;           // ... rt_reproject's result {r, g, b, n_out} ...
     DevBuf rp_counts;        // ... and its copy of the per-tile frame counts (int32, rt_ctx::rp_counts holds the same)
+    DevBuf hs_s2, rp_s2;     // rt_set_history_variance: the history's and the result's per-sample variance of y, one float per pixel
     DevBuf wbuf;             // pooled units (ordered / one chunk): per resident wave 64 x chunk_frames colours
     DevBuf finfo;            // exact near-first walk tables (variant 61)
     DevBuf f2inner, f2leaves;
@@ -96,6 +97,7 @@ struct rt_ctx : rt_impl::SceneState {
     // or stale since an upload, a camera or a BVH-mode change); ft_links_ok: Device::ft_links holds the
     // current tree's links (cleared with ft_valid); the argument block last copied to Device::ft_args
     bool ft_valid = false, ft_links_ok = false;
+    uint32_t ft_gen = 0;   // counts the rt_render_features passes queued: which pass the buffers hold
     std::vector<uint8_t> ft_args_host;
     // rt_history_capture: a history is held (Device::hs_*), of this size, made with this camera block,
     // whose matrix M is hs_M (rt.h); rt_reproject: a result is held (Device::rp_out), and the per-tile
@@ -105,6 +107,11 @@ struct rt_ctx : rt_impl::SceneState {
     rt_camera_ubo hs_cam{};
     float hs_M[9] = {0};
     std::vector<int32_t> rp_counts;
+    // rt_set_history_variance: the history and the result carry s2 (Device::hs_s2, rp_s2) while on; a held
+    // history or result was made under the current value (a change drops both).  rp_ft_gen: the ft_gen of the
+    // feature buffers the held result was made from (rt_denoise_reprojected filters over the same ones)
+    bool hist_var = false;
+    uint32_t rp_ft_gen = 0;
     // the first device's staged colours of the last launch (rt_debug_read_samples): frames, sparse flags
     int staged_frames = 0;
     bool staged_sparse = false;

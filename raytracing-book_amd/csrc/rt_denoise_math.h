@@ -37,6 +37,59 @@ RT_HD rt_dn4 dn_level0(const rt_dn4 img, float m2w, int n) {
     return o;
 }
 
+// Level 0 over a reprojected view (rt.h rt_denoise_reprojected): R = {r, g, b, n} the view, s2 the
+// per-sample variance of y that came with it (< 0 or NaN: unknown), ai the first-hit albedo_id words.
+// A pixel is bad when y(R) is not finite or n is not > 0.  Known s2: V_0 = s2 / n.  Otherwise the spread
+// of y over the 5x5 taps at spacing 1 (row-major, dy outer, centre included) that lie in the image, are
+// not bad and carry p's id word (a skipped tap is read at the clamped position and leaves the sums
+// untouched):  cnt = cnt + 1; sy = sy + y(q);  m = sy / cnt;  then e = y(q) - m; sd = sd + e * e over the
+// same taps;  V_0 = cnt < 2 ? +0 : (sd / (cnt - 1)) / n.
+RT_HD int dn_rp_bad(const rt_dn4 r) { return !(dn_finite(dn_lum(r)) && r.w > 0.0f); }
+RT_HD rt_dn4 dn_level0_reprojected(const rt_dn4* __restrict__ rgbn, const float* __restrict__ s2,
+                                   const rt_dn4* __restrict__ ai, int W, int H, int x, int y) {
+    const size_t p = (size_t)y * W + x;
+    const rt_dn4 R = rgbn[p];
+    rt_dn4 o = R;
+    if (dn_rp_bad(R)) {
+        o.w = -1.0f;
+        return o;
+    }
+    const float s = s2[p];
+    if (s >= 0.0f && dn_finite(s)) {
+        o.w = s / R.w;
+        return o;
+    }
+    const unsigned idp = rt_f2u(ai[p].w);
+    float yq[25];
+    unsigned ok = 0u;
+    float cnt = 0.0f, sy = 0.0f;
+#pragma unroll
+    for (int dy = -2; dy <= 2; dy++) {
+#pragma unroll
+        for (int dx = -2; dx <= 2; dx++) {
+            const int t = (dy + 2) * 5 + (dx + 2);
+            const int qx = x + dx, qy = y + dy;
+            const bool in = qx >= 0 && qx < W && qy >= 0 && qy < H;
+            const size_t q = (size_t)dn_clampi(qy, H - 1) * W + dn_clampi(qx, W - 1);
+            const rt_dn4 rq = rgbn[q];
+            const bool use = in && !dn_rp_bad(rq) && rt_f2u(ai[q].w) == idp;
+            yq[t] = dn_lum(rq);
+            ok |= use ? 1u << t : 0u;
+            cnt = use ? cnt + 1.0f : cnt;
+            sy = use ? sy + yq[t] : sy;
+        }
+    }
+    const float m = sy / cnt;
+    float sd = 0.0f;
+#pragma unroll
+    for (int t = 0; t < 25; t++) {
+        const float e = yq[t] - m;
+        sd = (ok >> t & 1u) ? sd + e * e : sd;
+    }
+    o.w = cnt < 2.0f ? 0.0f : (sd / (cnt - 1.0f)) / R.w;
+    return o;
+}
+
 // Vb(p): taps (dy, dx) in {-1, 0, 1}^2 at spacing 1, row-major; for each tap in the image and good
 //   acc = acc + (k3[dy] * k3[dx]) * V(q);  ws = ws + k3[dy] * k3[dx];     Vb = acc / ws.
 // A skipped tap is read at the clamped position and leaves acc and ws untouched.  Bad p: +0.

@@ -105,6 +105,7 @@ int rt_render_features(rt_ctx* c) {
     const int W = c->width, H = d.local_rows;
     const size_t n = (size_t)W * H;
     c->ft_valid = false;
+    c->ft_gen++;   // whatever the buffers held, a reprojected result made from it no longer matches them
     if ((r = ensure(c, d, d.ft_nd, n * sizeof(float4)))) return r;
     if ((r = ensure(c, d, d.ft_ai, n * sizeof(float4)))) return r;
     if (!c->ft_links_ok) {   // (the copy waits for the stream: a queued pass keeps the links it was given)

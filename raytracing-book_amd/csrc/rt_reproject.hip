@@ -11,6 +11,11 @@
 // arithmetic is rt_reproject_math.h's, shared with rt_reproject_host, which the result equals bit for bit.
 // history_kernel builds the history's {r, g, b, n} from the image and the per-tile counts; the first-hit
 // buffers are copied device to device.
+//
+// rt_set_history_variance(ctx, 1) switches both calls to instantiations of their own, history_var_kernel and
+// reproject_var_kernel, which carry the per-sample variance s2 of y beside the pixel: one more float read
+// per pixel (M2.w) and per tap (the history's s2, in the cache line of a neighbouring lane's), one more
+// written.  With the switch off the two kernels above are the ones launched, with nothing else allocated.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -58,6 +63,34 @@ __global__ void __launch_bounds__(256) reproject_kernel(const rt_dn4* __restrict
     dst[p] = rp_pixel(image[p], counts[tile], nd[p], ai[p], hc, hnd, hai, V, x, y);
 }
 
+// rt_set_history_variance: the history's pixel and its s2 from the image, M2.w and the counts
+__global__ void __launch_bounds__(256) history_var_kernel(const rt_dn4* __restrict__ image, const rt_dn4* __restrict__ moments,
+                                                          const int32_t* __restrict__ counts, int W, int H,
+                                                          rt_dn4* __restrict__ dst, float* __restrict__ dst_s2) {
+    int x, y, tile;
+    if (!tile_pixel(W, H, x, y, tile)) return;
+    const size_t p = (size_t)y * W + x;
+    const rt_dn4 img = image[p];
+    const int n = counts[tile];
+    dst[p] = rp_history_pixel(img, n);
+    dst_s2[p] = rp_history_s2(img, moments[p].w, n);
+}
+
+// ... and the gather that carries it: reproject_kernel's operations for the result word, s2 beside it
+__global__ void __launch_bounds__(256) reproject_var_kernel(const rt_dn4* __restrict__ image, const rt_dn4* __restrict__ moments,
+                                                            const int32_t* __restrict__ counts, const rt_dn4* __restrict__ nd,
+                                                            const rt_dn4* __restrict__ ai, const rt_dn4* __restrict__ hc,
+                                                            const rt_dn4* __restrict__ hnd, const rt_dn4* __restrict__ hai,
+                                                            const float* __restrict__ hs2, rt_rp_view V,
+                                                            rt_dn4* __restrict__ dst, float* __restrict__ dst_s2) {
+    int x, y, tile;
+    if (!tile_pixel(V.W, V.H, x, y, tile)) return;
+    const size_t p = (size_t)y * V.W + x;
+    float s2;
+    dst[p] = rp_pixel_var(image[p], counts[tile], nd[p], ai[p], hc, hnd, hai, V, x, y, moments[p].w, hs2, &s2);
+    dst_s2[p] = s2;
+}
+
 }  // namespace
 
 namespace rt_impl {
@@ -71,6 +104,8 @@ void reproject_free(rt_ctx* c) {
         dev_free(d.hs_ai);
         dev_free(d.rp_out);
         dev_free(d.rp_counts);
+        dev_free(d.hs_s2);
+        dev_free(d.rp_s2);
     }
     c->rp_counts.clear();
     c->hs_valid = c->rp_valid = false;
@@ -132,7 +167,7 @@ int rt_history_capture(rt_ctx* c, int source) {
             return set_err(c, RT_ERR_STATE, "rt_history_capture: the tile counts need rt_set_moments(ctx, 1) first");
         if (c->moments_frames < 1 && c->tile_frames.empty())
             return set_err(c, RT_ERR_STATE, "rt_history_capture: no tile holds a frame (rt_render from frame 1 first)");
-    } else if (!c->rp_valid || !d.rp_out.ptr) {
+    } else if (!c->rp_valid || !d.rp_out.ptr || (c->hist_var && !d.rp_s2.ptr)) {
         return set_err(c, RT_ERR_STATE, "rt_history_capture: no reprojected result held (rt_reproject first)");
     }
     if ((r = features_ready(c, "rt_history_capture"))) return r;
@@ -148,15 +183,23 @@ int rt_history_capture(rt_ctx* c, int source) {
     if ((r = ensure(c, d, d.hs_px, bytes))) return r;
     if ((r = ensure(c, d, d.hs_nd, bytes))) return r;
     if ((r = ensure(c, d, d.hs_ai, bytes))) return r;
+    if (c->hist_var && (r = ensure(c, d, d.hs_s2, n * sizeof(float)))) return r;
     if (from_image) {
         if ((r = upload_counts(c, d, nt, "rt_history_capture"))) return r;
-        hipLaunchKernelGGL(history_kernel, dim3((unsigned)((nt + kTilesPerBlock - 1) / kTilesPerBlock)), dim3(256), 0, d.stream,
-                           (const rt_dn4*)d.image_ptr, (const int32_t*)d.rp_counts.ptr, W, H, (rt_dn4*)d.hs_px.ptr);
+        if (c->hist_var)
+            hipLaunchKernelGGL(history_var_kernel, dim3((unsigned)((nt + kTilesPerBlock - 1) / kTilesPerBlock)), dim3(256), 0,
+                               d.stream, (const rt_dn4*)d.image_ptr, (const rt_dn4*)d.m2.ptr, (const int32_t*)d.rp_counts.ptr, W,
+                               H, (rt_dn4*)d.hs_px.ptr, (float*)d.hs_s2.ptr);
+        else
+            hipLaunchKernelGGL(history_kernel, dim3((unsigned)((nt + kTilesPerBlock - 1) / kTilesPerBlock)), dim3(256), 0,
+                               d.stream, (const rt_dn4*)d.image_ptr, (const int32_t*)d.rp_counts.ptr, W, H, (rt_dn4*)d.hs_px.ptr);
         const hipError_t e = hipGetLastError();
         if (e != hipSuccess)
             return set_err(c, RT_ERR_DEVICE, std::string("rt_history_capture launch failed: ") + hipGetErrorString(e));
     } else {
         HIPCHK(c, hipMemcpyAsync(d.hs_px.ptr, d.rp_out.ptr, bytes, hipMemcpyDeviceToDevice, d.stream));
+        if (c->hist_var)
+            HIPCHK(c, hipMemcpyAsync(d.hs_s2.ptr, d.rp_s2.ptr, n * sizeof(float), hipMemcpyDeviceToDevice, d.stream));
     }
     HIPCHK(c, hipMemcpyAsync(d.hs_nd.ptr, d.ft_nd.ptr, bytes, hipMemcpyDeviceToDevice, d.stream));
     HIPCHK(c, hipMemcpyAsync(d.hs_ai.ptr, d.ft_ai.ptr, bytes, hipMemcpyDeviceToDevice, d.stream));
@@ -177,7 +220,7 @@ int rt_reproject(rt_ctx* c, const rt_reproject_params* params) {
     int r = reproject_ready(c, "rt_reproject");
     if (r) return r;
     Device& d = c->devs[0];
-    if (!c->hs_valid || !d.hs_px.ptr || !d.hs_nd.ptr || !d.hs_ai.ptr)
+    if (!c->hs_valid || !d.hs_px.ptr || !d.hs_nd.ptr || !d.hs_ai.ptr || (c->hist_var && !d.hs_s2.ptr))
         return set_err(c, RT_ERR_STATE, "rt_reproject: no history held (rt_history_capture first)");
     if (c->hs_w != c->width || c->hs_h != d.local_rows)
         return set_err(c, RT_ERR_STATE, "rt_reproject: the image's size is not the history's (rt_history_capture again)");
@@ -190,6 +233,7 @@ int rt_reproject(rt_ctx* c, const rt_reproject_params* params) {
     const int nt = ((W + 7) / 8) * ((H + 7) / 8);
     c->rp_valid = false;
     if ((r = ensure(c, d, d.rp_out, n * sizeof(rt_dn4)))) return r;
+    if (c->hist_var && (r = ensure(c, d, d.rp_s2, n * sizeof(float)))) return r;
     if ((r = upload_counts(c, d, nt, "rt_reproject"))) return r;
     rt_rp_view V;
     V.cam = c->cam;
@@ -200,12 +244,20 @@ int rt_reproject(rt_ctx* c, const rt_reproject_params* params) {
     V.max_history = prm.max_history;
     V.W = W;
     V.H = H;
-    hipLaunchKernelGGL(reproject_kernel, dim3((unsigned)((nt + kTilesPerBlock - 1) / kTilesPerBlock)), dim3(256), 0, d.stream,
-                       (const rt_dn4*)d.image_ptr, (const int32_t*)d.rp_counts.ptr, (const rt_dn4*)d.ft_nd.ptr,
-                       (const rt_dn4*)d.ft_ai.ptr, (const rt_dn4*)d.hs_px.ptr, (const rt_dn4*)d.hs_nd.ptr,
-                       (const rt_dn4*)d.hs_ai.ptr, V, (rt_dn4*)d.rp_out.ptr);
+    const dim3 grid((unsigned)((nt + kTilesPerBlock - 1) / kTilesPerBlock));
+    if (c->hist_var)
+        hipLaunchKernelGGL(reproject_var_kernel, grid, dim3(256), 0, d.stream, (const rt_dn4*)d.image_ptr, (const rt_dn4*)d.m2.ptr,
+                           (const int32_t*)d.rp_counts.ptr, (const rt_dn4*)d.ft_nd.ptr, (const rt_dn4*)d.ft_ai.ptr,
+                           (const rt_dn4*)d.hs_px.ptr, (const rt_dn4*)d.hs_nd.ptr, (const rt_dn4*)d.hs_ai.ptr,
+                           (const float*)d.hs_s2.ptr, V, (rt_dn4*)d.rp_out.ptr, (float*)d.rp_s2.ptr);
+    else
+        hipLaunchKernelGGL(reproject_kernel, grid, dim3(256), 0, d.stream, (const rt_dn4*)d.image_ptr,
+                           (const int32_t*)d.rp_counts.ptr, (const rt_dn4*)d.ft_nd.ptr, (const rt_dn4*)d.ft_ai.ptr,
+                           (const rt_dn4*)d.hs_px.ptr, (const rt_dn4*)d.hs_nd.ptr, (const rt_dn4*)d.hs_ai.ptr, V,
+                           (rt_dn4*)d.rp_out.ptr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_err(c, RT_ERR_DEVICE, std::string("rt_reproject launch failed: ") + hipGetErrorString(e));
+    c->rp_ft_gen = c->ft_gen;
     c->rp_valid = true;
     return RT_OK;
 }
@@ -219,6 +271,27 @@ int rt_read_reprojected(rt_ctx* c, float* rgbn) {
     Device& d = c->devs[0];
     HIPCHK(c, hipSetDevice(d.id));
     return d2h(c, d, rgbn, d.rp_out.ptr, (size_t)d.local_rows * c->width * 16);
+}
+
+int rt_set_history_variance(rt_ctx* c, int on) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if ((on != 0) == c->hist_var) return RT_OK;
+    c->hist_var = on != 0;
+    c->hs_valid = c->rp_valid = false;   // what is held was made under the other value
+    return RT_OK;
+}
+
+int rt_read_reprojected_variance(rt_ctx* c, float* s2) {
+    if (!c || !s2) return RT_ERR_INVALID_ARG;
+    if (!c->rp_valid || !c->hist_var || c->devs.size() != 1 || !c->devs[0].rp_s2.ptr)
+        return set_err(c, RT_ERR_STATE,
+                       "rt_read_reprojected_variance: no reprojected result with variance held (rt_set_history_variance(ctx, 1) "
+                       "and rt_reproject first)");
+    int r = rt_sync(c);
+    if (r) return r;
+    Device& d = c->devs[0];
+    HIPCHK(c, hipSetDevice(d.id));
+    return d2h(c, d, s2, d.rp_s2.ptr, (size_t)d.local_rows * c->width * sizeof(float));
 }
 
 }  // extern "C"

@@ -1,6 +1,7 @@
 // rt_reproject_host.cpp — the host half of temporal reprojection (rt.h rt_reproject): the parameter
 // resolve and the history view's matrix that rt_history_capture and rt_reproject share with the host
-// reference, and rt_reproject_host, rt_reproject_math.h's functions over caller arrays.  Plain C++, no device.
+// reference, and rt_reproject_host, rt_reproject_variance_host and rt_history_variance_host, rt_reproject_math.h's
+// functions over caller arrays.  Plain C++, no device.
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -51,10 +52,13 @@ int reproject_matrix(const rt_camera_ubo& cam, float M[9]) {
 
 }  // namespace rt_impl
 
-extern "C" int rt_reproject_host(const float* history_rgbn, const float* history_nd, const float* history_ai,
-                                 const float history_camera[28], const float* image, const int32_t* tile_frames, int n_tiles,
-                                 const float* normal_depth, const float* albedo_id, const float camera[28], int width,
-                                 int height, const rt_reproject_params* params, float* rgbn_out) {
+namespace {
+
+// rt_reproject_host (history_s2, m2, s2_out NULL) and rt_reproject_variance_host over caller arrays
+int reproject_host(const float* history_rgbn, const float* history_nd, const float* history_ai, const float* history_s2,
+                   const float history_camera[28], const float* image, const float* m2, const int32_t* tile_frames, int n_tiles,
+                   const float* normal_depth, const float* albedo_id, const float camera[28], int width, int height,
+                   const rt_reproject_params* params, float* rgbn_out, float* s2_out) {
     if (!history_rgbn || !history_nd || !history_ai || !history_camera || !image || !tile_frames || !normal_depth ||
         !albedo_id || !camera || !rgbn_out)
         return RT_ERR_INVALID_ARG;
@@ -83,6 +87,8 @@ extern "C" int rt_reproject_host(const float* history_rgbn, const float* history
         std::memcpy(hc.data(), history_rgbn, n * sizeof(rt_dn4));
         std::memcpy(hnd.data(), history_nd, n * sizeof(rt_dn4));
         std::memcpy(hai.data(), history_ai, n * sizeof(rt_dn4));
+        std::vector<float> hs2;
+        if (s2_out) hs2.assign(history_s2, history_s2 + n);
         for (int y = 0; y < height; y++)
             for (int x = 0; x < width; x++) {
                 const size_t p = (size_t)y * width + x;
@@ -90,12 +96,59 @@ extern "C" int rt_reproject_host(const float* history_rgbn, const float* history
                 std::memcpy(&img, image + p * 4, sizeof(img));
                 std::memcpy(&nd, normal_depth + p * 4, sizeof(nd));
                 std::memcpy(&ai, albedo_id + p * 4, sizeof(ai));
-                const rt_dn4 o = rp_pixel(img, tile_frames[(size_t)(y >> 3) * tiles_x + (x >> 3)], nd, ai, hc.data(),
-                                          hnd.data(), hai.data(), V, x, y);
+                const int count = tile_frames[(size_t)(y >> 3) * tiles_x + (x >> 3)];
+                rt_dn4 o;
+                if (s2_out) {
+                    float s2;
+                    o = rp_pixel_var(img, count, nd, ai, hc.data(), hnd.data(), hai.data(), V, x, y, m2[p * 4 + 3], hs2.data(), &s2);
+                    s2_out[p] = s2;
+                } else {
+                    o = rp_pixel(img, count, nd, ai, hc.data(), hnd.data(), hai.data(), V, x, y);
+                }
                 std::memcpy(rgbn_out + p * 4, &o, sizeof(o));
             }
     } catch (const std::bad_alloc&) {
         return RT_ERR_NOMEM;
     }
+    return RT_OK;
+}
+
+}  // namespace
+
+extern "C" int rt_reproject_host(const float* history_rgbn, const float* history_nd, const float* history_ai,
+                                 const float history_camera[28], const float* image, const int32_t* tile_frames, int n_tiles,
+                                 const float* normal_depth, const float* albedo_id, const float camera[28], int width,
+                                 int height, const rt_reproject_params* params, float* rgbn_out) {
+    return reproject_host(history_rgbn, history_nd, history_ai, nullptr, history_camera, image, nullptr, tile_frames, n_tiles,
+                          normal_depth, albedo_id, camera, width, height, params, rgbn_out, nullptr);
+}
+
+extern "C" int rt_reproject_variance_host(const float* history_rgbn, const float* history_nd, const float* history_ai,
+                                          const float* history_s2, const float history_camera[28], const float* image,
+                                          const float* m2, const int32_t* tile_frames, int n_tiles, const float* normal_depth,
+                                          const float* albedo_id, const float camera[28], int width, int height,
+                                          const rt_reproject_params* params, float* rgbn_out, float* s2_out) {
+    if (!history_s2 || !m2 || !s2_out) return RT_ERR_INVALID_ARG;
+    return reproject_host(history_rgbn, history_nd, history_ai, history_s2, history_camera, image, m2, tile_frames, n_tiles,
+                          normal_depth, albedo_id, camera, width, height, params, rgbn_out, s2_out);
+}
+
+extern "C" int rt_history_variance_host(const float* image, const float* m2, const int32_t* tile_frames, int n_tiles, int width,
+                                        int height, float* s2_out) {
+    if (!image || !m2 || !tile_frames || !s2_out) return RT_ERR_INVALID_ARG;
+    if (width < 1 || height < 1 || width > RT_MAX_IMAGE_DIM || height > RT_MAX_IMAGE_DIM ||
+        (size_t)width * height > ((size_t)1 << 30))
+        return RT_ERR_INVALID_ARG;
+    const int tiles_x = (width + 7) / 8, tiles_y = (height + 7) / 8;
+    if (n_tiles != tiles_x * tiles_y) return RT_ERR_INVALID_ARG;
+    for (int t = 0; t < n_tiles; t++)
+        if (tile_frames[t] < 0) return RT_ERR_INVALID_ARG;
+    for (int y = 0; y < height; y++)
+        for (int x = 0; x < width; x++) {
+            const size_t p = (size_t)y * width + x;
+            rt_dn4 img;
+            std::memcpy(&img, image + p * 4, sizeof(img));
+            s2_out[p] = rp_history_s2(img, m2[p * 4 + 3], tile_frames[(size_t)(y >> 3) * tiles_x + (x >> 3)]);
+        }
     return RT_OK;
 }

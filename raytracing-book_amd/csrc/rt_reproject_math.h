@@ -32,14 +32,33 @@ RT_HD rt_dn4 rp_history_pixel(const rt_dn4 img, int count) {
     return o;
 }
 
+// The per-sample variance of y = (r + g) + b that travels with the history (rt.h rt_set_history_variance):
+// g_max(0, M2.w / (n - 1)) with rp_history_pixel's n, or -1 = unknown (fewer than two frames, M2.w not
+// finite).  Every "known" test is written `s2 >= 0`, so a NaN is unknown.
+RT_HD float rp_history_s2(const rt_dn4 img, float m2w, int count) {
+    const float n = rp_rgb_finite(img) ? (float)count : 0.0f;
+    if (n >= 2.0f && dn_finite(m2w)) return g_max(0.0f, m2w / (n - 1.0f));
+    return -1.0f;
+}
+
 // The result at current pixel (x, y): img its image word, count its tile's frame count, nd / ai its
 // first-hit words; hc / hnd / hai the history's {r, g, b, n} and first-hit buffers (V.W x V.H each).
-RT_HD rt_dn4 rp_pixel(const rt_dn4 img, int count, const rt_dn4 nd, const rt_dn4 ai, const rt_dn4* __restrict__ hc,
-                      const rt_dn4* __restrict__ hnd, const rt_dn4* __restrict__ hai, const rt_rp_view& V, int x, int y) {
+// VAR: the variance is carried too (m2w the pixel's M2.w, hs2 the history's s2, one float per pixel; the
+// result's s2 goes to *s2_out).  The {r, g, b, n_out} word comes out of the same operations either way;
+// VAR = false compiles to rt_reproject as it was and touches none of the three.
+template <bool VAR>
+RT_HD rt_dn4 rp_pixel_t(const rt_dn4 img, int count, const rt_dn4 nd, const rt_dn4 ai, const rt_dn4* __restrict__ hc,
+                        const rt_dn4* __restrict__ hnd, const rt_dn4* __restrict__ hai, const rt_rp_view& V, int x, int y,
+                        float m2w, const float* __restrict__ hs2, float* __restrict__ s2_out) {
     const int W = V.W, H = V.H;
     rt_dn4 out = img;
     const float n_c = rp_rgb_finite(img) ? (float)count : 0.0f;
     out.w = n_c;
+    float s2_c = -1.0f;
+    if (VAR) {
+        s2_c = rp_history_s2(img, m2w, count);
+        *s2_out = s2_c;   // what every `return out` below leaves: not reprojected, or rejected
+    }
     // 1. a miss, or first-hit words that are not finite: nothing to reproject
     if (!(dn_guide_good(nd, ai) && dn_guide_hit(ai))) return out;
     // 2. the world point the pixel's centre ray lands on
@@ -59,6 +78,7 @@ RT_HD rt_dn4 rp_pixel(const rt_dn4 img, int count, const rt_dn4 nd, const rt_dn4
     const int ix = (int)x0, iy = (int)y0;   // -1 .. W - 1, -1 .. H - 1
     // 4. the four taps
     float sw = 0.0f, sr = 0.0f, sg = 0.0f, sb = 0.0f, sn = 0.0f;
+    float ss = 0.0f, sws = 0.0f;   // VAR: the taps whose s2 is known, and their weights
 #pragma unroll
     for (int j = 0; j < 2; j++) {
 #pragma unroll
@@ -81,18 +101,27 @@ RT_HD rt_dn4 rp_pixel(const rt_dn4 img, int count, const rt_dn4 nd, const rt_dn4
             sg = use ? sg + u * hq.y : sg;
             sb = use ? sb + u * hq.z : sb;
             sn = use ? sn + u * hq.w : sn;
+            if (VAR) {
+                const float s = hs2[q];
+                const bool kn = use && s >= 0.0f;
+                ss = kn ? ss + u * s : ss;
+                sws = kn ? sws + u : sws;
+            }
         }
     }
     // 5. the history estimate
     if (!(sw > 0.0f)) return out;
     const float hr = sr / sw, hg = sg / sw, hb = sb / sw;
     const float n_hist = g_min(sn / sw, V.max_history);
+    float s2_hist = -1.0f;
+    if (VAR) s2_hist = sws > 0.0f ? ss / sws : -1.0f;
     // 6. blended with the pixel's own frames by the counts
     if (n_c == 0.0f) {
         out.x = hr;
         out.y = hg;
         out.z = hb;
         out.w = n_hist;
+        if (VAR) *s2_out = s2_hist;
         return out;
     }
     const float n_out = n_c + n_hist, alpha = n_hist / n_out;
@@ -100,7 +129,22 @@ RT_HD rt_dn4 rp_pixel(const rt_dn4 img, int count, const rt_dn4 nd, const rt_dn4
     out.y = img.y + alpha * (hg - img.y);
     out.z = img.z + alpha * (hb - img.z);
     out.w = n_out;
+    if (VAR) {
+        // s2 blends like a colour channel: the count-weighted mean of the two per-sample variances
+        if (!(s2_c >= 0.0f)) *s2_out = s2_hist;
+        else if (!(s2_hist >= 0.0f)) *s2_out = s2_c;
+        else *s2_out = s2_c + alpha * (s2_hist - s2_c);
+    }
     return out;
+}
+RT_HD rt_dn4 rp_pixel(const rt_dn4 img, int count, const rt_dn4 nd, const rt_dn4 ai, const rt_dn4* __restrict__ hc,
+                      const rt_dn4* __restrict__ hnd, const rt_dn4* __restrict__ hai, const rt_rp_view& V, int x, int y) {
+    return rp_pixel_t<false>(img, count, nd, ai, hc, hnd, hai, V, x, y, 0.0f, nullptr, nullptr);
+}
+RT_HD rt_dn4 rp_pixel_var(const rt_dn4 img, int count, const rt_dn4 nd, const rt_dn4 ai, const rt_dn4* __restrict__ hc,
+                          const rt_dn4* __restrict__ hnd, const rt_dn4* __restrict__ hai, const rt_rp_view& V, int x, int y,
+                          float m2w, const float* __restrict__ hs2, float* __restrict__ s2_out) {
+    return rp_pixel_t<true>(img, count, nd, ai, hc, hnd, hai, V, x, y, m2w, hs2, s2_out);
 }
 
 // The parameters after defaults and checks (rt_reproject_host.cpp reproject_resolve).

@@ -165,6 +165,16 @@ def _amd_protos(L, old_rev=False):
         _proto(L, "rt_read_reprojected", i, vp, c_float_p)
         _proto(L, "rt_reproject_host", i, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, i32_p, i, c_float_p,
                c_float_p, c_float_p, i, i, rp_p, c_float_p)
+    if not old_rev or hasattr(L, "rt_set_history_variance"):   # ... or from before the variance carried through reprojection
+        dp_p, gp_p = ctypes.POINTER(RtDenoiseParams), ctypes.POINTER(RtGuideParams)
+        rp_p, i32_p = ctypes.POINTER(RtReprojectParams), ctypes.POINTER(ctypes.c_int32)
+        _proto(L, "rt_set_history_variance", i, vp, i)
+        _proto(L, "rt_read_reprojected_variance", i, vp, c_float_p)
+        _proto(L, "rt_denoise_reprojected", i, vp, dp_p, gp_p)
+        _proto(L, "rt_history_variance_host", i, c_float_p, c_float_p, i32_p, i, i, i, c_float_p)
+        _proto(L, "rt_reproject_variance_host", i, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
+               i32_p, i, c_float_p, c_float_p, c_float_p, i, i, rp_p, c_float_p, c_float_p)
+        _proto(L, "rt_denoise_reprojected_host", i, c_float_p, c_float_p, c_float_p, c_float_p, i, i, dp_p, gp_p, c_float_p)
     _proto(L, "rt_abi_version", i)
     _proto(L, "rt_create", i, i, c_int_p, ctypes.POINTER(vp))
     _proto(L, "rt_destroy", i, vp)

@@ -369,6 +369,84 @@ def reproject_host(history, history_nd, history_ai, history_camera, image, tile_
     return out
 
 
+def _tile_frames_of(tile_frames, W, H):
+    tf = np.ascontiguousarray(tile_frames, dtype=np.int32).ravel()
+    if tf.size == 1:
+        tf = np.full(((W + 7) // 8) * ((H + 7) // 8), tf[0], np.int32)
+    return tf
+
+
+def history_variance_host(image, m2, tile_frames, lib=None):
+    """rt_history_variance_host (host only): what rt_history_capture keeps as s2 under set_history_variance():
+    [H, W] float32 from an [H, W, 4] image, its M2 and one frame count per 8x8 tile (a scalar stands for every
+    tile); -1 where unknown."""
+    L = lib or _lib.amd()
+    img = np.ascontiguousarray(image, dtype=np.float32)
+    mom = np.ascontiguousarray(m2, dtype=np.float32)
+    if img.ndim != 3 or img.shape[2] != 4 or mom.shape != img.shape:
+        raise ValueError("image and m2 are [H, W, 4]")
+    H, W = img.shape[:2]
+    tf = _tile_frames_of(tile_frames, W, H)
+    out = np.empty((H, W), np.float32)
+    rc = L.rt_history_variance_host(img.ctypes.data_as(c_float_p), mom.ctypes.data_as(c_float_p),
+                                    tf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(tf.size), W, H,
+                                    out.ctypes.data_as(c_float_p))
+    if rc != 0:
+        raise RTError(rc, "rt_history_variance_host: one count >= 0 per 8x8 tile required")
+    return out
+
+
+def reproject_variance_host(history, history_nd, history_ai, history_s2, history_camera, image, m2, tile_frames, normal_depth,
+                            albedo_id, camera, cos_min=None, kz=None, max_history=None, lib=None):
+    """rt_reproject_variance_host (host only): reproject_host with the history's s2 [H, W] and the current
+    view's M2 [H, W, 4] -> ([H, W, 4] float32 (r, g, b, n_out), [H, W] float32 s2)."""
+    L = lib or _lib.amd()
+    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (history, history_nd, history_ai, image, m2, normal_depth, albedo_id)]
+    img = arrs[3]
+    if img.ndim != 3 or img.shape[2] != 4 or any(a.shape != img.shape for a in arrs):
+        raise ValueError("history, image, m2 and the first-hit buffers are [H, W, 4]")
+    hs2 = np.ascontiguousarray(history_s2, dtype=np.float32)
+    if hs2.shape != img.shape[:2]:
+        raise ValueError("history_s2 is [H, W]")
+    cams = [np.ascontiguousarray(c, dtype=np.float32).ravel() for c in (history_camera, camera)]
+    if any(c.size != 28 for c in cams):
+        raise ValueError("a camera block is 28 floats")
+    H, W = img.shape[:2]
+    tf = _tile_frames_of(tile_frames, W, H)
+    out, s2 = np.empty_like(img), np.empty((H, W), np.float32)
+    fp = lambda a: a.ctypes.data_as(c_float_p)  # noqa: E731
+    rc = L.rt_reproject_variance_host(fp(arrs[0]), fp(arrs[1]), fp(arrs[2]), fp(hs2), fp(cams[0]), fp(img), fp(arrs[4]),
+                                      tf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(tf.size), fp(arrs[5]), fp(arrs[6]),
+                                      fp(cams[1]), W, H, _reproject_params(cos_min, kz, max_history), fp(out), fp(s2))
+    if rc != 0:
+        raise RTError(rc, "rt_reproject_variance_host: cos_min in [-1, 1], kz >= 0, max_history > 0, one count >= 0 per 8x8 "
+                          "tile and a history camera with independent pixel deltas and view corner required")
+    return out, s2
+
+
+def denoise_reprojected_host(rgbn, s2, normal_depth, albedo_id, levels=None, k=None, guides=True, lib=None):
+    """rt_denoise_reprojected_host (host only): the preview filter over a reprojected view [H, W, 4] (r, g, b, n)
+    and its s2 [H, W] -> [H, W, 4] float32 (w = 1).  guides: (kn, kz, ka), True for the library's defaults,
+    None / False for the unguided filter."""
+    L = lib or _lib.amd()
+    arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (rgbn, normal_depth, albedo_id)]
+    img = arrs[0]
+    if img.ndim != 3 or img.shape[2] != 4 or any(a.shape != img.shape for a in arrs):
+        raise ValueError("rgbn, normal_depth and albedo_id are [H, W, 4]")
+    v = np.ascontiguousarray(s2, dtype=np.float32)
+    if v.shape != img.shape[:2]:
+        raise ValueError("s2 is [H, W]")
+    H, W = img.shape[:2]
+    g = (0.0, 0.0, 0.0) if guides is None or guides is False else guides
+    out = np.empty_like(img)
+    fp = lambda a: a.ctypes.data_as(c_float_p)  # noqa: E731
+    rc = L.rt_denoise_reprojected_host(fp(img), fp(v), fp(arrs[1]), fp(arrs[2]), W, H, _denoise_params(levels, k),
+                                       _guide_params(g), fp(out))
+    if rc != 0:
+        raise RTError(rc, "rt_denoise_reprojected_host: levels 1..5, k > 0, kn, kz, ka >= 0 required")
+    return out
+
+
 SHAPES = {0: "fast-lds", 1: "fast-global", 2: "link-lds", 3: "meta-lds", 4: "meta-global", 5: "link-two-level"}
 
 
@@ -659,6 +737,27 @@ class RenderContext:
         """rt_read_reprojected: the result as [H, W, 4] float32 (r, g, b, n_out)."""
         out = np.empty((self.local_rows, self.width, 4), dtype=np.float32)
         self._check(self._L.rt_read_reprojected(self._h, out.ctypes.data_as(c_float_p)))
+        return out
+
+    def set_history_variance(self, on=True):
+        """rt_set_history_variance: carry the per-sample variance of y with the history and the reprojected
+        result (off by default; a change drops both)."""
+        self._check(self._L.rt_set_history_variance(self._h, 1 if on else 0))
+
+    def read_reprojected_variance(self):
+        """rt_read_reprojected_variance: the result's s2 as [H, W] float32 (negative: unknown)."""
+        out = np.empty((self.local_rows, self.width), dtype=np.float32)
+        self._check(self._L.rt_read_reprojected_variance(self._h, out.ctypes.data_as(c_float_p)))
+        return out
+
+    def denoise_reprojected(self, levels=None, k=None, guides=True):
+        """rt_denoise_reprojected + rt_read_denoised: the preview filter over the reprojected view, [H, W, 4]
+        float32 (w = 1).  Needs set_history_variance() and reproject().  guides: (kn, kz, ka), True for the
+        library's defaults, None / False for the unguided filter (all-zero strengths)."""
+        g = (0.0, 0.0, 0.0) if guides is None or guides is False else guides
+        self._check(self._L.rt_denoise_reprojected(self._h, _denoise_params(levels, k), _guide_params(g)))
+        out = np.empty((self.local_rows, self.width, 4), dtype=np.float32)
+        self._check(self._L.rt_read_denoised(self._h, out.ctypes.data_as(c_float_p)))
         return out
 
     def read_samples(self):
