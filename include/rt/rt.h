@@ -540,6 +540,80 @@ int rt_denoise_reprojected_host(const float* rgbn, const float* s2, const float*
                                 int width, int height, const rt_denoise_params* params, const rt_guide_params* guides,
                                 float* rgba_out);
 
+/* ---- The presented frame: compose, expose and tonemap on the device ----------------------------------
+ * The display path of the reference (Texture.saveAsPNG: float -> unorm8 -> gamma table, what
+ * rts_tonemap_rgb8 does on the host) as one kernel over a buffer the context holds, so a preview leaves the
+ * device as 4 bytes per pixel.  RT_PRESENT_MOVED also composes the picture recommended after a camera move:
+ * the filtered buffer where the reprojected view's count did not grow, the reprojected view elsewhere.
+ * It writes buffers of its own: image, moments, counts, features, history, the reprojected result and the
+ * denoised buffer keep their bits, and a context that never calls these allocates and runs nothing new.
+ * Single-device contexts without rt_set_partition (RT_ERR_STATE).
+ *
+ * The definition.  All arithmetic is f32 without contraction: one multiplication per channel, rintf (round
+ * half to even) and comparisons, so a float32 restatement matches bit for bit.  For the pixel p of a W x H
+ * image: cnt = the frame count of p's 8x8 tile, n_t = (float)cnt; R = the reprojected word (r, g, b, n_out);
+ * D = the denoised buffer (rt_read_denoised's).
+ *   1. Colour.  RT_PRESENT_IMAGE, RT_PRESENT_DENOISED, RT_PRESENT_REPROJECTED: c = that buffer's rgb, w = 1.
+ *      RT_PRESENT_MOVED: fresh = !(R.w > n_t) (a NaN count is fresh);  c = fresh ? D.rgb : R.rgb;
+ *      w = fresh ? 1 : 0.  (A bad pixel passes through the filter unchanged, so D is R there.)
+ *   2. Exposure.  e.c = c.c * exposure for c in r, g, b.  (1.0f keeps every finite value's bits and a NaN a NaN.)
+ *   3. Code.  code(f) = 0 if !(f > 0);  255 if f >= 1;  otherwise (int)rintf(f * 255.0f).
+ *   4. Packing.  byte(f) = lut[code(f)], lut the 256-entry gamma table of Texture.saveAsPNG
+ *      (lut[b] = (byte)((float)pow(b / 255.0, 1 / 2.2) * 255.0f), built on the host, never on the device);
+ *      the pixel's word is byte(e.r) | byte(e.g) << 8 | byte(e.b) << 16 | 0xFFu << 24: in memory r, g, b, 255.
+ *   5. Float copy.  With keep_float, (e.r, e.g, e.b, w) is written as well.
+ * csrc/rt_present_math.h holds these operations once, for the kernel and for rt_present_host;
+ * host/rt_gamma_lut.h holds the table once, for them and for rts_tonemap_rgb8, whose bytes the r, g, b of
+ * RT_PRESENT_IMAGE at exposure 1 equal.
+ *
+ * source is one of the four values, exposure > 0 and finite, reserved 0 (RT_ERR_INVALID_ARG otherwise);
+ * NULL = RT_PRESENT_IMAGE, exposure 1, no float copy. */
+enum { RT_PRESENT_IMAGE = 0, RT_PRESENT_DENOISED = 1, RT_PRESENT_REPROJECTED = 2, RT_PRESENT_MOVED = 3 };
+typedef struct rt_present_params { int source; float exposure; int keep_float; int reserved[5]; /* must be 0 */ } rt_present_params;
+
+/* Queue the kernel on the context's stream behind what is queued.  RT_ERR_STATE naming what is lacking:
+ * no image (RT_PRESENT_IMAGE); no filtered image held (RT_PRESENT_DENOISED); no reprojected result held
+ * (RT_PRESENT_REPROJECTED, RT_PRESENT_MOVED); for RT_PRESENT_MOVED also rt_set_moments off (the tile counts),
+ * or a denoised buffer that rt_denoise_reprojected did not write from the result now held (none, one that
+ * rt_denoise / rt_denoise_guided wrote since, or a result that rt_reproject replaced since).  The counts are
+ * the current ones, as rt_reproject reads them.  The frame (4 bytes per pixel, with keep_float 16 more; both
+ * allocated by the first call that needs them, with 256 bytes for the table) is held until the next
+ * rt_present, rt_resize or rt_destroy. */
+int rt_present(rt_ctx* ctx, const rt_present_params* params);
+/* rt_sync, then the frame as W*H*4 bytes (r, g, b, 255); RT_ERR_STATE with no frame held. */
+int rt_read_presented(rt_ctx* ctx, uint8_t* rgba8);
+/* rt_sync, then the float copy as W*H*4 floats (e.r, e.g, e.b, w); RT_ERR_STATE unless the frame held was
+ * made with keep_float. */
+int rt_read_presented_float(rt_ctx* ctx, float* rgbw);
+/* As rt_bind_device_image, for the frame: later rt_present calls write it into caller-owned device memory of
+ * at least W*H*4 bytes, 4-byte aligned (RT_ERR_INVALID_ARG otherwise), on the context's stream (rt_set_stream:
+ * a torch uint8 tensor of shape (H, W, 4) receives the frame on torch's current stream).  NULL returns to the
+ * internal buffer.  Either way no frame is held until the next rt_present; rt_resize lets the buffer go. */
+int rt_bind_device_present(rt_ctx* ctx, void* device_ptr, size_t nbytes);
+/* Host only, no device: the same header's arithmetic over caller arrays.  image, denoised, reprojected: W*H*4
+ * floats each, needed as the source reads them (RT_PRESENT_MOVED: reprojected, denoised and tile_frames, one
+ * count >= 0 per 8x8 tile, row-major, n_tiles = ceil(W/8) * ceil(H/8)); the others may be NULL.  rgba8_out:
+ * W*H*4 bytes; rgbw_out: W*H*4 floats, written and needed with keep_float alone.  RT_ERR_INVALID_ARG for
+ * anything else, and for bad params. */
+int rt_present_host(const float* image, const float* denoised, const float* reprojected, const int32_t* tile_frames,
+                    int n_tiles, int width, int height, const rt_present_params* params, uint8_t* rgba8_out,
+                    float* rgbw_out);
+
+/* One call per pose of a moving camera.  It is this sequence of the calls above and nothing else, queued with
+ * no rt_sync between the steps, each step's refusal returned unchanged:
+ *   1. rt_history_capture: RT_HISTORY_FROM_REPROJECTED if a result is held for the pose being left (made from
+ *      the feature buffers now held, and those current), else RT_HISTORY_FROM_IMAGE, which needs what that
+ *      call needs: current features and tile counts that are not all 0;
+ *   2. rt_set_camera(camera);   3. rt_render(1, n_frames, rand_factors);   4. rt_render_features;
+ *   5. rt_reproject(reproject);
+ *   6. rt_denoise_reprojected(denoise, guides), under rt_set_history_variance(ctx, 1) alone;
+ *   7. rt_present(present); a NULL present is exposure 1, no float copy and RT_PRESENT_MOVED under
+ *      rt_set_history_variance(ctx, 1), RT_PRESENT_REPROJECTED without it.  RT_PRESENT_MOVED without the
+ *      variance is rt_present's RT_ERR_STATE: no rt_denoise_reprojected wrote the denoised buffer. */
+int rt_render_moved(rt_ctx* ctx, const float camera[28], int n_frames, const float* rand_factors,
+                    const rt_reproject_params* reproject, const rt_denoise_params* denoise,
+                    const rt_guide_params* guides, const rt_present_params* present);
+
 /* Per-frame u_rand_factor for frame index f (0-based) of a seeded render:
  * top 24 bits of splitmix64(seed, f) / 2^24, in [0,1).  Stands in for the
  * reference's (float)Math.random() per frame (RaytraceExecutor.java:124). */

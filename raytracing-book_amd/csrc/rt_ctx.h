@@ -1,5 +1,5 @@
 // rt_ctx.h — the context behind the C ABI's rt_ctx handle and the device helpers its
-// translation units share (rt_capi.hip, rt_comm.hip, rt_debug.hip, rt_denoise.hip, rt_features.hip, rt_reproject.hip).  Internal to the libraries.
+// translation units share (rt_capi.hip, rt_comm.hip, rt_debug.hip, rt_denoise.hip, rt_features.hip, rt_reproject.hip, rt_present.hip).  Internal to the libraries.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -57,6 +57,10 @@ struct Device {
     DevBuf rp_out;           // ... rt_reproject's result {r, g, b, n_out} ...
     DevBuf rp_counts;        // ... and its copy of the per-tile frame counts (int32, rt_ctx::rp_counts holds the same)
     DevBuf hs_s2, rp_s2;     // rt_set_history_variance: the history's and the result's per-sample variance of y, one float per pixel
+    DevBuf pr_out, pr_float; // rt_present: the frame's internal buffer, one rgba8 dword per pixel, and its float4 copy (rt_present.hip) ...
+    DevBuf pr_lut;           // ... and the 256-byte gamma table (rt_gamma_lut.h), copied once
+    void* pr_ptr = nullptr;  // ... the active frame buffer (internal or bound: rt_bind_device_present)
+    bool pr_bound = false;
     DevBuf wbuf;             // pooled units (ordered / one chunk): per resident wave 64 x chunk_frames colours
     DevBuf finfo;            // exact near-first walk tables (variant 61)
     DevBuf f2inner, f2leaves;
@@ -112,6 +116,11 @@ struct rt_ctx : rt_impl::SceneState {
     // feature buffers the held result was made from (rt_denoise_reprojected filters over the same ones)
     bool hist_var = false;
     uint32_t rp_ft_gen = 0;
+    // rp_gen counts the rt_reproject results made (the held one is the rp_gen-th); dn_rp_gen: the rp_gen of the
+    // result rt_denoise_reprojected wrote the denoised buffer from, 0 when another filter call wrote it or none did
+    uint32_t rp_gen = 0, dn_rp_gen = 0;
+    // rt_present: a frame is held in Device::pr_ptr, and a float copy of it in Device::pr_float
+    bool pr_valid = false, pr_float_valid = false;
     // the first device's staged colours of the last launch (rt_debug_read_samples): frames, sparse flags
     int staged_frames = 0;
     bool staged_sparse = false;
@@ -238,5 +247,8 @@ inline int validate(rt_ctx* c) { return validate(*c, &c->err); }
 // rt_comm.hip (the RCCL table and its state stay in that unit)
 int device_gather(rt_ctx* c);
 void comm_destroy(Device& d);   // rt_destroy: frees the device's communicator, if any
+// rt_reproject.hip: the current per-tile frame counts (nt of them) in Device::rp_counts, copied when they differ
+// from the ones it holds; `what` names the caller in the message (rt_present's RT_PRESENT_MOVED reads them too)
+int reproject_upload_counts(rt_ctx* c, Device& d, int nt, const char* what);
 
 }  // namespace rt_impl

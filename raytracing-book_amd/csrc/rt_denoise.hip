@@ -166,6 +166,7 @@ int run_denoise(rt_ctx* c, const rt_denoise_params* params, const rt_guide_resol
         c->dn_counts.swap(counts);
     }
     c->dn_result = -1;
+    c->dn_rp_gen = 0;
     const dim3 block(kBX, kBY), grid((unsigned)((W + kBX - 1) / kBX), (unsigned)((H + kBY - 1) / kBY));
     hipLaunchKernelGGL(dn_prologue_kernel, grid, block, 0, d.stream, (const rt_dn4*)d.image_ptr, (const rt_dn4*)d.m2.ptr,
                        (const int32_t*)d.dn_counts.ptr, W, H, (rt_dn4*)d.dn_px[0].ptr);
@@ -200,10 +201,13 @@ int run_denoise_reprojected(rt_ctx* c, const rt_denoise_params* params, const rt
     if ((r = ensure(c, d, d.dn_px[1], n * sizeof(rt_dn4)))) return r;
     if ((r = ensure(c, d, d.dn_vb, n * sizeof(float)))) return r;
     c->dn_result = -1;
+    c->dn_rp_gen = 0;
     const dim3 block(kBX, kBY), grid((unsigned)((W + kBX - 1) / kBX), (unsigned)((H + kBY - 1) / kBY));
     hipLaunchKernelGGL(dn_prologue_reprojected_kernel, grid, block, 0, d.stream, (const rt_dn4*)d.rp_out.ptr,
                        (const float*)d.rp_s2.ptr, (const rt_dn4*)d.ft_ai.ptr, W, H, (rt_dn4*)d.dn_px[0].ptr);
-    return run_levels(c, d, W, H, prm, &guides, "rt_denoise_reprojected");
+    if ((r = run_levels(c, d, W, H, prm, &guides, "rt_denoise_reprojected"))) return r;
+    c->dn_rp_gen = c->rp_gen;   // the buffer holds this result, filtered (rt_present's RT_PRESENT_MOVED)
+    return RT_OK;
 }
 
 }  // namespace

@@ -112,6 +112,21 @@ void reproject_free(rt_ctx* c) {
     c->hs_w = c->hs_h = 0;
 }
 
+// the per-tile counts on the device, copied when they differ from the ones it holds
+int reproject_upload_counts(rt_ctx* c, Device& d, int nt, const char* what) {
+    std::vector<int32_t> counts = c->tile_frames;
+    if (counts.empty()) counts.assign((size_t)nt, c->moments_frames);
+    if ((int)counts.size() != nt) return set_err(c, RT_ERR_STATE, std::string(what) + ": the tile counts do not match the image");
+    if (counts != c->rp_counts || !d.rp_counts.ptr) {
+        c->rp_counts.clear();
+        int r;
+        if ((r = ensure(c, d, d.rp_counts, (size_t)nt * sizeof(int32_t)))) return r;
+        if ((r = h2d(c, d, d.rp_counts.ptr, counts.data(), (size_t)nt * sizeof(int32_t)))) return r;
+        c->rp_counts.swap(counts);
+    }
+    return RT_OK;
+}
+
 }  // namespace rt_impl
 
 using namespace rt_impl;
@@ -132,21 +147,6 @@ int features_ready(rt_ctx* c, const char* what) {
     if (!(c->ft_valid && d.ft_nd.ptr && d.ft_ai.ptr))
         return set_err(c, RT_ERR_STATE,
                        std::string(what) + ": no first-hit features held for the current scene and camera (rt_render_features first)");
-    return RT_OK;
-}
-
-// the per-tile counts on the device, copied when they differ from the ones it holds
-int upload_counts(rt_ctx* c, Device& d, int nt, const char* what) {
-    std::vector<int32_t> counts = c->tile_frames;
-    if (counts.empty()) counts.assign((size_t)nt, c->moments_frames);
-    if ((int)counts.size() != nt) return set_err(c, RT_ERR_STATE, std::string(what) + ": the tile counts do not match the image");
-    if (counts != c->rp_counts || !d.rp_counts.ptr) {
-        c->rp_counts.clear();
-        int r;
-        if ((r = ensure(c, d, d.rp_counts, (size_t)nt * sizeof(int32_t)))) return r;
-        if ((r = h2d(c, d, d.rp_counts.ptr, counts.data(), (size_t)nt * sizeof(int32_t)))) return r;
-        c->rp_counts.swap(counts);
-    }
     return RT_OK;
 }
 
@@ -185,7 +185,7 @@ int rt_history_capture(rt_ctx* c, int source) {
     if ((r = ensure(c, d, d.hs_ai, bytes))) return r;
     if (c->hist_var && (r = ensure(c, d, d.hs_s2, n * sizeof(float)))) return r;
     if (from_image) {
-        if ((r = upload_counts(c, d, nt, "rt_history_capture"))) return r;
+        if ((r = reproject_upload_counts(c, d, nt, "rt_history_capture"))) return r;
         if (c->hist_var)
             hipLaunchKernelGGL(history_var_kernel, dim3((unsigned)((nt + kTilesPerBlock - 1) / kTilesPerBlock)), dim3(256), 0,
                                d.stream, (const rt_dn4*)d.image_ptr, (const rt_dn4*)d.m2.ptr, (const int32_t*)d.rp_counts.ptr, W,
@@ -234,7 +234,7 @@ int rt_reproject(rt_ctx* c, const rt_reproject_params* params) {
     c->rp_valid = false;
     if ((r = ensure(c, d, d.rp_out, n * sizeof(rt_dn4)))) return r;
     if (c->hist_var && (r = ensure(c, d, d.rp_s2, n * sizeof(float)))) return r;
-    if ((r = upload_counts(c, d, nt, "rt_reproject"))) return r;
+    if ((r = reproject_upload_counts(c, d, nt, "rt_reproject"))) return r;
     rt_rp_view V;
     V.cam = c->cam;
     V.cam_h = c->hs_cam;
@@ -258,6 +258,7 @@ int rt_reproject(rt_ctx* c, const rt_reproject_params* params) {
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_err(c, RT_ERR_DEVICE, std::string("rt_reproject launch failed: ") + hipGetErrorString(e));
     c->rp_ft_gen = c->ft_gen;
+    c->rp_gen++;   // another result: a denoised buffer made from the one before is not this one's (rt_present)
     c->rp_valid = true;
     return RT_OK;
 }

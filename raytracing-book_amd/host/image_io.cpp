@@ -6,6 +6,7 @@
 //   3. RGB PNG, row 0 = top.
 #include "rt/rt_scene.h"
 #include "rt/rt.h"
+#include "rt_gamma_lut.h"
 
 #include <zlib.h>
 
@@ -22,16 +23,7 @@ uint8_t unorm8(float f) {
     return (uint8_t)std::lrintf(f * 255.0f);
 }
 
-struct GammaLut {
-    uint8_t v[256];
-    GammaLut() {
-        for (int b = 0; b < 256; b++) {
-            float corrected = (float)std::pow(b / 255.0, 1.0 / 2.2) * 255.0f;
-            v[b] = (uint8_t)(int8_t)(int)corrected;
-        }
-    }
-};
-const GammaLut kGamma;
+const rt_gamma_lut kGamma;   // step 2's table (rt_gamma_lut.h, shared with rt_present)
 
 void put_be32(std::vector<uint8_t>& o, uint32_t x) {
     o.push_back(x >> 24); o.push_back(x >> 16); o.push_back(x >> 8); o.push_back(x);

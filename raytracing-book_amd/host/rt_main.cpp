@@ -39,6 +39,13 @@
 // before it is saved: -o receives the filtered image, and so does every --preview update once two
 // frames exist; --raw-output <png> also saves the image as rendered.  One device; works with --noise
 // and --adaptive.
+//
+// A moving camera: --moves <K> --move-shift <S> --move-frames <N> turns the sample moments and the history
+// variance on and, after the normal render, takes the camera through K poses, each S viewport widths along
+// pixel_delta_u from the one before (camera_pos and up_left shifted by the same vector), with N frames per
+// pose through rt_render_moved: history kept, the new view rendered, reprojected, filtered and presented on
+// the device.  Each pose's frame (rt_read_presented, alpha dropped) is saved as <output stem>.moveNN.png.
+// The frames of pose k (1-based) take the factors of frame indices spp + (k - 1) * N onwards.  One device; needs -o.
 #include "rt/rt.h"
 #include "rt/rt_scene.h"
 
@@ -64,7 +71,7 @@ struct Opt {
 };
 
 // commons-cli Options in Main.getOptions order (Main.java:43-70)
-enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_DENOISE, O_DENOISE_LEVELS, O_DENOISE_K, O_RAW_OUT, O_DENOISE_GUIDES, O_DENOISE_KN, O_DENOISE_KZ, O_DENOISE_KA, O_FEATURES_OUT, O_N };
+enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_DENOISE, O_DENOISE_LEVELS, O_DENOISE_K, O_RAW_OUT, O_DENOISE_GUIDES, O_DENOISE_KN, O_DENOISE_KZ, O_DENOISE_KA, O_FEATURES_OUT, O_MOVES, O_MOVE_SHIFT, O_MOVE_FRAMES, O_N };
 const Opt kOpts[O_N] = {
     {"h", "help", false, "print help message"},
     {"s", "scene", true, "scene ID"},
@@ -90,6 +97,9 @@ const Opt kOpts[O_N] = {
     {nullptr, "denoise-kz", true, "with --denoise-guides: strength of the depth term, >= 0"},
     {nullptr, "denoise-ka", true, "with --denoise-guides: strength of the albedo term, >= 0"},
     {nullptr, "features-output", true, "save first-hit <arg>_normal.png, <arg>_albedo.png and <arg>_depth.png"},
+    {nullptr, "moves", true, "after the render: this many camera poses, each saved as <output stem>.moveNN.png"},
+    {nullptr, "move-shift", true, "with --moves: viewport widths each pose moves sideways from the one before"},
+    {nullptr, "move-frames", true, "with --moves: frames rendered at each pose (reprojected, filtered, presented)"},
 };
 
 // HelpFormatter.printHelp("OpenGL Ray Tracer", options): options sorted by key.
@@ -301,6 +311,25 @@ int main(int argc, char** argv) {
     if (seen[O_FEATURES_OUT] && devices.size() > 1)
         die("rtrender", "--features-output renders on one device (--devices names more)");
 
+    const bool moving = seen[O_MOVES];
+    int moves = 0, move_frames = 0;
+    float move_shift = 0.0f;
+    if (!moving && (seen[O_MOVE_SHIFT] || seen[O_MOVE_FRAMES])) die("rtrender", "--move-shift and --move-frames go with --moves");
+    if (moving) {
+        if (!seen[O_MOVE_SHIFT] || !seen[O_MOVE_FRAMES])
+            die("rtrender", "--moves needs --move-shift <S> and --move-frames <N>");
+        moves = parse_int(val[O_MOVES]);
+        move_frames = parse_int(val[O_MOVE_FRAMES]);
+        if (moves < 1) die("rtrender", "--moves must be at least 1");
+        if (move_frames < 1) die("rtrender", "--move-frames must be at least 1");
+        char* end = nullptr;
+        move_shift = std::strtof(val[O_MOVE_SHIFT].c_str(), &end);
+        if (val[O_MOVE_SHIFT].empty() || *end != '\0' || !(move_shift >= -3.0e38f && move_shift <= 3.0e38f))
+            die("rtrender", "--move-shift must be a finite number");
+        if (devices.size() > 1) die("rtrender", "--moves renders on one device (--devices names more)");
+        if (output.empty()) die("rtrender", "--moves needs -o <png> (the poses are saved beside it)");
+    }
+
     rts_scene* scene = nullptr;
     if (rts_build(scene_id, width, height, (uint64_t)seed, nullptr, &scene) != 0) die("rts_build", rts_last_error());
     rts_info info;
@@ -332,9 +361,11 @@ int main(int argc, char** argv) {
     rts_spp_uniforms(spp, &sqrt_spp, &recip);   // RaytraceExecutor.setSamplePerPixel
     chk(rt_set_params(ctx, max_depth, info.background, sqrt_spp, recip), "rt_set_params");
     chk(rt_resize(ctx, width, height), "rt_resize");
-    if (denoise) chk(rt_set_moments(ctx, 1), "rt_set_moments");
+    if (denoise || moving) chk(rt_set_moments(ctx, 1), "rt_set_moments");
+    if (moving) chk(rt_set_history_variance(ctx, 1), "rt_set_history_variance");
     // the first-hit pass, once: the scene and the camera do not change from here on
-    if (guides || !features_output.empty()) chk(rt_render_features(ctx), "rt_render_features");
+    // (with --moves the scene and the first pose's camera: rt_render_moved renders each later pose's)
+    if (guides || !features_output.empty() || moving) chk(rt_render_features(ctx), "rt_render_features");
     // the image to save: through the filter with --denoise (once every tile holds two frames), else as rendered
     auto read_shown = [&](float* px, bool filtered) {
         if (filtered && guides) {
@@ -467,6 +498,37 @@ int main(int argc, char** argv) {
             char abs_path[PATH_MAX];
             const char* shown = realpath(nm.c_str(), abs_path) ? abs_path : nm.c_str();
             std::printf("A first-hit feature image has been saved to: %s\n", shown);
+        }
+    }
+    if (moving) {
+        // the poses: rt_render_moved each, the presented frame out as 4 bytes per pixel
+        const size_t n = (size_t)width * height;
+        const size_t dot = output.rfind('.');
+        const bool has_ext = dot != std::string::npos && output.find('/', dot) == std::string::npos && dot > 0;
+        const std::string stem = has_ext ? output.substr(0, dot) : output;
+        std::vector<float> mrf((size_t)move_frames);
+        std::vector<uint8_t> rgba8(n * 4), rgb8(n * 3);
+        const float step = (float)((double)move_shift * width);
+        for (int k = 1; k <= moves; k++) {
+            for (int c = 0; c < 3; c++) {
+                const float v = ubo[12 + c] * step;
+                ubo[4 + c] += v;
+                ubo[8 + c] += v;
+            }
+            for (int i = 0; i < move_frames; i++)
+                mrf[(size_t)i] = rt_frame_rand_factor((uint64_t)seed, (uint64_t)spp + (uint64_t)(k - 1) * move_frames + i);
+            chk(rt_render_moved(ctx, ubo, move_frames, mrf.data(), nullptr, nullptr, nullptr, nullptr), "rt_render_moved");
+            chk(rt_read_presented(ctx, rgba8.data()), "rt_read_presented");
+            for (size_t i = 0; i < n; i++)
+                for (int c = 0; c < 3; c++) rgb8[i * 3 + c] = rgba8[i * 4 + c];
+            char num[32];
+            std::snprintf(num, sizeof(num), ".move%02d.png", k);
+            const std::string name = stem + num;
+            if (rts_save_png_rgb8(rgb8.data(), width, height, name.c_str()) != 0)
+                uncaught("java.lang.RuntimeException", "Failed to save texture as PNG");
+            char abs_path[PATH_MAX];
+            const char* shown = realpath(name.c_str(), abs_path) ? abs_path : name.c_str();
+            std::printf("Move %d/%d: %d frame(s), saved to: %s\n", k, moves, move_frames, shown);
         }
     }
     rt_destroy(ctx);

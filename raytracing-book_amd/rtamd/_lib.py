@@ -95,6 +95,12 @@ class RtReprojectParams(ctypes.Structure):
                 ("reserved", ctypes.c_int * 5)]
 
 
+class RtPresentParams(ctypes.Structure):
+    """rt.h rt_present_params."""
+    _fields_ = [("source", ctypes.c_int), ("exposure", ctypes.c_float), ("keep_float", ctypes.c_int),
+                ("reserved", ctypes.c_int * 5)]
+
+
 RT_FEATURE_MISS = 0xFFFFFFFF   # rt.h
 
 RT_PK_N = 33   # rt_debug.h RT_PK_N
@@ -175,6 +181,16 @@ def _amd_protos(L, old_rev=False):
         _proto(L, "rt_reproject_variance_host", i, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
                i32_p, i, c_float_p, c_float_p, c_float_p, i, i, rp_p, c_float_p, c_float_p)
         _proto(L, "rt_denoise_reprojected_host", i, c_float_p, c_float_p, c_float_p, c_float_p, i, i, dp_p, gp_p, c_float_p)
+    if not old_rev or hasattr(L, "rt_present"):   # ... or from before the presented frame
+        dp_p, gp_p = ctypes.POINTER(RtDenoiseParams), ctypes.POINTER(RtGuideParams)
+        rp_p, i32_p = ctypes.POINTER(RtReprojectParams), ctypes.POINTER(ctypes.c_int32)
+        pp_p, u8_p = ctypes.POINTER(RtPresentParams), ctypes.POINTER(ctypes.c_uint8)
+        _proto(L, "rt_present", i, vp, pp_p)
+        _proto(L, "rt_read_presented", i, vp, u8_p)
+        _proto(L, "rt_read_presented_float", i, vp, c_float_p)
+        _proto(L, "rt_bind_device_present", i, vp, vp, sz)
+        _proto(L, "rt_present_host", i, c_float_p, c_float_p, c_float_p, i32_p, i, i, i, pp_p, u8_p, c_float_p)
+        _proto(L, "rt_render_moved", i, vp, c_float_p, i, c_float_p, rp_p, dp_p, gp_p, pp_p)
     _proto(L, "rt_abi_version", i)
     _proto(L, "rt_create", i, i, c_int_p, ctypes.POINTER(vp))
     _proto(L, "rt_destroy", i, vp)

@@ -447,6 +447,47 @@ def denoise_reprojected_host(rgbn, s2, normal_depth, albedo_id, levels=None, k=N
     return out
 
 
+PRESENT_SOURCES = {"image": 0, "denoised": 1, "reprojected": 2, "moved": 3}   # rt.h RT_PRESENT_*
+
+
+def _present_params(source, exposure, keep_float):
+    """rt_present_params for (source, exposure, keep_float)."""
+    p = _lib.RtPresentParams()
+    p.source = PRESENT_SOURCES[source] if isinstance(source, str) else int(source)
+    p.exposure = float(exposure)
+    p.keep_float = 1 if keep_float else 0
+    return ctypes.byref(p)
+
+
+def present_host(source="image", image=None, denoised=None, reprojected=None, tile_frames=None, exposure=1.0,
+                 keep_float=False, lib=None):
+    """rt_present_host (host only, no device): the presented frame of the [H, W, 4] float32 buffers the source
+    reads ("moved": reprojected, denoised and one frame count per 8x8 tile, row-major; a scalar stands for
+    every tile) -> [H, W, 4] uint8 (r, g, b, 255), with keep_float (that, the float copy [H, W, 4] float32)."""
+    L = lib or _lib.amd()
+    arrs = [None if a is None else np.ascontiguousarray(a, dtype=np.float32) for a in (image, denoised, reprojected)]
+    given = [a for a in arrs if a is not None]
+    if not given or any(a.ndim != 3 or a.shape[2] != 4 or a.shape != given[0].shape for a in given):
+        raise ValueError("image, denoised and reprojected are [H, W, 4]")
+    H, W = given[0].shape[:2]
+    tf = None
+    if tile_frames is not None:
+        tf = np.ascontiguousarray(tile_frames, dtype=np.int32).ravel()
+        if tf.size == 1:
+            tf = np.full(((W + 7) // 8) * ((H + 7) // 8), tf[0], np.int32)
+    out = np.empty((H, W, 4), np.uint8)
+    flt = np.empty((H, W, 4), np.float32) if keep_float else None
+    fp = lambda a: None if a is None else a.ctypes.data_as(c_float_p)  # noqa: E731
+    rc = L.rt_present_host(fp(arrs[0]), fp(arrs[1]), fp(arrs[2]),
+                           None if tf is None else tf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)),
+                           0 if tf is None else int(tf.size), W, H, _present_params(source, exposure, keep_float),
+                           out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), fp(flt))
+    if rc != 0:
+        raise RTError(rc, "rt_present_host: a source of RT_PRESENT_* with the buffers it reads, exposure > 0 and finite, "
+                          "one count >= 0 per 8x8 tile required")
+    return (out, flt) if keep_float else out
+
+
 SHAPES = {0: "fast-lds", 1: "fast-global", 2: "link-lds", 3: "meta-lds", 4: "meta-global", 5: "link-two-level"}
 
 
@@ -743,6 +784,7 @@ class RenderContext:
         """rt_set_history_variance: carry the per-sample variance of y with the history and the reprojected
         result (off by default; a change drops both)."""
         self._check(self._L.rt_set_history_variance(self._h, 1 if on else 0))
+        self._history_variance = bool(on)
 
     def read_reprojected_variance(self):
         """rt_read_reprojected_variance: the result's s2 as [H, W] float32 (negative: unknown)."""
@@ -759,6 +801,54 @@ class RenderContext:
         out = np.empty((self.local_rows, self.width, 4), dtype=np.float32)
         self._check(self._L.rt_read_denoised(self._h, out.ctypes.data_as(c_float_p)))
         return out
+
+    # -- the presented frame (rt.h rt_present / rt_render_moved)
+    def read_presented(self):
+        """rt_read_presented: the frame held as [H, W, 4] uint8 (r, g, b, 255)."""
+        out = np.empty((self.local_rows, self.width, 4), dtype=np.uint8)
+        self._check(self._L.rt_read_presented(self._h, out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8))))
+        return out
+
+    def present(self, source="image", exposure=1.0, keep_float=False):
+        """rt_present + rt_read_presented: compose ("moved"), expose and tonemap on the device -> [H, W, 4] uint8.
+        source: "image", "denoised", "reprojected" or "moved" (the filtered buffer where the reprojected view's
+        count did not grow, the reprojected view elsewhere).  keep_float: read_presented_float() has the
+        exposed floats."""
+        self._check(self._L.rt_present(self._h, _present_params(source, exposure, keep_float)))
+        return self.read_presented()
+
+    def read_presented_float(self):
+        """rt_read_presented_float: the frame's float copy [H, W, 4] float32 (e.r, e.g, e.b, w); w is 1 but
+        where "moved" shows the reprojected view.  Needs a present(keep_float=True)."""
+        out = np.empty((self.local_rows, self.width, 4), dtype=np.float32)
+        self._check(self._L.rt_read_presented_float(self._h, out.ctypes.data_as(c_float_p)))
+        return out
+
+    def bind_device_present(self, ptr, nbytes=0):
+        """rt_bind_device_present: later frames go to caller-owned device memory (a torch uint8 tensor's
+        data_ptr() of at least H * W * 4 bytes), on the context's stream; None / 0 returns to the internal buffer."""
+        self._check(self._L.rt_bind_device_present(self._h, ctypes.c_void_p(ptr or None), ctypes.c_size_t(nbytes)))
+
+    def render_moved(self, camera, rand_factors, source=None, exposure=1.0, keep_float=False, cos_min=None, kz=None,
+                     max_history=None, levels=None, k=None, guides=True):
+        """rt_render_moved + rt_read_presented: one pose of a moving camera -> [H, W, 4] uint8.  Captures the
+        history, moves to `camera` (28 floats), renders len(rand_factors) frames from frame 1 and the features,
+        reprojects, filters (under set_history_variance()) and presents.  source None: the library's choice
+        ("moved" under set_history_variance(), else "reprojected") unless exposure or keep_float ask for
+        parameters, then the same choice made here.  The other arguments are reproject()'s and denoise_reprojected()'s."""
+        cam = np.ascontiguousarray(camera, dtype=np.float32).ravel()
+        assert cam.size == 28
+        rf = np.ascontiguousarray(rand_factors, dtype=np.float32)
+        if source is None and float(exposure) == 1.0 and not keep_float:
+            pp = None
+        else:
+            src = source if source is not None else ("moved" if getattr(self, "_history_variance", False) else "reprojected")
+            pp = _present_params(src, exposure, keep_float)
+        g = (0.0, 0.0, 0.0) if guides is None or guides is False else guides
+        self._check(self._L.rt_render_moved(self._h, cam.ctypes.data_as(c_float_p), int(rf.size), rf.ctypes.data_as(c_float_p),
+                                            _reproject_params(cos_min, kz, max_history), _denoise_params(levels, k),
+                                            _guide_params(g), pp))
+        return self.read_presented()
 
     def read_samples(self):
         """rt_debug_read_samples: the last launch's staged colours, [n_frames, local_rows, W, 4]."""
