@@ -614,6 +614,81 @@ int rt_render_moved(rt_ctx* ctx, const float camera[28], int n_frames, const flo
                     const rt_reproject_params* reproject, const rt_denoise_params* denoise,
                     const rt_guide_params* guides, const rt_present_params* present);
 
+/* ---- After a move: extra frames on the tiles the history does not reach ------------------------------
+ * Where the old view saw the surface a pixel of the reprojected view holds n_hist + n frames, and one more
+ * adds next to nothing; a disoccluded strip, a rejected tap or the leading edge holds the pose's own n,
+ * usually 1.  rt_reach_tiles reduces the reprojected result's count n_out to one record per 8x8 tile on the
+ * device, rt_refine_select chooses tiles from the records on the host, and rt_render_moved_refined spends
+ * extra frames on the chosen tiles inside the one call per pose, reading back 16 bytes per tile.  The records
+ * are a buffer of their own (allocated by the first rt_reach_tiles; a context that never calls these
+ * allocates and runs nothing new): image, moments, counts, features, history, the reprojected result, the
+ * denoised buffer and the presented frame keep their bits.  Single-device contexts without
+ * rt_set_partition (RT_ERR_STATE).
+ *
+ * The record.  One per 8x8 tile of the image, tiles row-major, ceil(W/8) per row (the tiles of
+ * rt_read_tile_sums), made from the held rt_reproject result R = (r, g, b, n_out) and a threshold min_count.
+ * All arithmetic is f32 without contraction, using only +, comparisons, fabsf and rt_glsl.h's g_min
+ * (g_min(a, b) = b < a ? b : a), so a float32 restatement matches bit for bit.  Lane ty*8+tx holds the pixel
+ * (tile_x*8+tx, tile_y*8+ty); `in` is true when that pixel lies in the image.  With n = R.w:
+ *   good  = in && n > 0 && fabsf(n) <= FLT_MAX        (a NaN is not good);
+ *   short = in && !(n >= min_count)                   (a NaN and a count of 0 are short);
+ *   v_min = good ? n : +inf;   v_sum = good ? n : +0;
+ *   for off = 32, 16, 8, 4, 2, 1 (every lane at once, x[lane ^ off] its partner's value before the step):
+ *     v_sum = v_sum + v_sum[lane ^ off];   v_min = g_min(v_min, v_min[lane ^ off]);
+ *   n_min = lane 0's v_min (+inf when the tile has no good pixel);   n_sum = lane 0's v_sum;
+ *   short_px = the number of short lanes;   pixels = the number of lanes that are in.
+ * csrc/rt_refine_math.h holds these operations once, for the kernel and for rt_tile_reach_host. */
+typedef struct rt_tile_reach { float n_min, n_sum; uint32_t short_px, pixels; } rt_tile_reach;  /* 16 bytes */
+/* min_count: 0 = automatic, (float)(n_frames + extra_frames), "short of what the refinement would give it";
+ * otherwise > 0 and finite.  extra_frames >= 0 (0: no refinement).  min_pixels 1 .. 64, 0 means 1.
+ * max_tiles 0 (no cap) or positive.  reserved 0.  RT_ERR_INVALID_ARG otherwise. */
+typedef struct rt_refine_params { float min_count; int extra_frames, min_pixels, max_tiles; int reserved[4]; /* must be 0 */ } rt_refine_params;
+
+/* Queue the kernel on the context's stream behind what is queued.  The record buffer is n_tiles * 16 bytes,
+ * allocated by the first call.  RT_ERR_INVALID_ARG unless min_count > 0 and finite.  RT_ERR_STATE naming what
+ * is lacking: no reprojected result held (rt_reproject first), a multi-device context or one under
+ * rt_set_partition.  The records belong to the result they were made from: they are held until the next
+ * rt_reach_tiles, rt_reproject, rt_resize or rt_destroy. */
+int rt_reach_tiles(rt_ctx* ctx, float min_count);
+/* rt_sync, then the records.  out may be NULL to query *n_tiles; RT_ERR_LIMIT if cap is short;
+ * RT_ERR_STATE with no records held. */
+int rt_read_tile_reach(rt_ctx* ctx, rt_tile_reach* out, int cap, int* n_tiles);
+/* Host only, no device: the same header's arithmetic over a caller array.  rgbn: W*H*4 floats (r, g, b, n_out),
+ * as rt_read_reprojected gives them; n_tiles = ceil(W/8) * ceil(H/8) and min_count > 0 and finite
+ * (RT_ERR_INVALID_ARG otherwise). */
+int rt_tile_reach_host(const float* rgbn, int width, int height, float min_count, rt_tile_reach* out, int n_tiles);
+/* Host only, pure.  A tile is a candidate when short_px >= min_pixels, min_pixels in 1 .. 64.  max_tiles 0: every
+ * candidate is active.  max_tiles > 0: t is the smallest value in min_pixels .. 65 for which at most max_tiles
+ * tiles have short_px >= t, and exactly those tiles are active.  Tiles with equal short_px stay or go together
+ * -- a tile's index never decides -- so fewer than max_tiles may be active, and none when more than max_tiles
+ * tiles share the largest count.  In particular, after a move that leaves every tile entirely fresh (all 64)
+ * a cap below the tile count selects none: when the whole view is new there is nothing to favour, and the
+ * pose's own n_frames are all it gets.  RT_ERR_INVALID_ARG: min_pixels outside 1 .. 64, max_tiles < 0, a
+ * short_px over 64, NULL tiles or active_out with n_tiles > 0.  n_active may be NULL. */
+int rt_refine_select(const rt_tile_reach* tiles, int n_tiles, int min_pixels, int max_tiles, uint8_t* active_out,
+                     int* n_active);
+/* rt_render_moved with extra frames where the history does not reach.  With refine NULL or extra_frames 0 it is
+ * rt_render_moved exactly.  Otherwise it is this sequence of the public calls and nothing else, each step's
+ * refusal returned unchanged:
+ *   rt_render_moved's steps 1 - 5 (capture, camera, rt_render(1, n_frames, rand_factors), features, reproject);
+ *   a. rt_reach_tiles(mc), mc = refine->min_count if that is > 0, else (float)(n_frames + extra_frames);
+ *   b. rt_read_tile_reach -- the call's one rt_sync;
+ *   c. rt_refine_select(min_pixels, max_tiles);
+ *   d. if any tile is active: rt_set_active_tiles(mask) (NULL when every tile is active),
+ *      rt_render(n_frames + 1, extra_frames, rand_factors + n_frames), rt_set_active_tiles(NULL, 0), and
+ *      rt_reproject(reproject) again over the same history (rt_render leaves the feature buffers current);
+ *   rt_render_moved's steps 6 and 7 (rt_denoise_reprojected, rt_present), over the second result.
+ * A refined tile holds, in image and moments, the bits of a plain (n_frames + extra_frames)-frame render and
+ * its count says so; rt_present's fresh test reads that count, so a refined pixel the history does not reach
+ * still takes the filtered buffer.  rand_factors holds n_frames + extra_frames values.  *tiles_refined
+ * (may be NULL) receives the number of tiles refined.  RT_ERR_STATE if a caller mask is set on entry (as
+ * rt_render_adaptive); no mask is left set, also when a step refuses.  RT_ERR_INVALID_ARG for bad refine
+ * params (rt_refine_params above). */
+int rt_render_moved_refined(rt_ctx* ctx, const float camera[28], int n_frames, const float* rand_factors,
+                            const rt_refine_params* refine, const rt_reproject_params* reproject,
+                            const rt_denoise_params* denoise, const rt_guide_params* guides,
+                            const rt_present_params* present, int* tiles_refined);
+
 /* Per-frame u_rand_factor for frame index f (0-based) of a seeded render:
  * top 24 bits of splitmix64(seed, f) / 2^24, in [0,1).  Stands in for the
  * reference's (float)Math.random() per frame (RaytraceExecutor.java:124). */

@@ -1,5 +1,5 @@
 // rt_ctx.h — the context behind the C ABI's rt_ctx handle and the device helpers its
-// translation units share (rt_capi.hip, rt_comm.hip, rt_debug.hip, rt_denoise.hip, rt_features.hip, rt_reproject.hip, rt_present.hip).  Internal to the libraries.
+// translation units share (rt_capi.hip, rt_comm.hip, rt_debug.hip, rt_denoise.hip, rt_features.hip, rt_reproject.hip, rt_present.hip, rt_refine.hip).  Internal to the libraries.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -61,6 +61,7 @@ struct Device {
     DevBuf pr_lut;           // ... and the 256-byte gamma table (rt_gamma_lut.h), copied once
     void* pr_ptr = nullptr;  // ... the active frame buffer (internal or bound: rt_bind_device_present)
     bool pr_bound = false;
+    DevBuf rf_tiles;         // rt_reach_tiles: one rt_tile_reach per 8x8 tile (rt_refine.hip)
     DevBuf wbuf;             // pooled units (ordered / one chunk): per resident wave 64 x chunk_frames colours
     DevBuf finfo;            // exact near-first walk tables (variant 61)
     DevBuf f2inner, f2leaves;
@@ -121,6 +122,8 @@ struct rt_ctx : rt_impl::SceneState {
     uint32_t rp_gen = 0, dn_rp_gen = 0;
     // rt_present: a frame is held in Device::pr_ptr, and a float copy of it in Device::pr_float
     bool pr_valid = false, pr_float_valid = false;
+    // rt_reach_tiles: the rp_gen of the result the reach records in Device::rf_tiles were made from, 0 when none are held
+    uint32_t rf_rp_gen = 0;
     // the first device's staged colours of the last launch (rt_debug_read_samples): frames, sparse flags
     int staged_frames = 0;
     bool staged_sparse = false;

@@ -25,6 +25,7 @@
 #include "rt_gamma_lut.h"
 #include "rt_present.h"
 #include "rt_present_math.h"
+#include "rt_refine.h"
 
 namespace {
 
@@ -243,13 +244,31 @@ int rt_render_moved(rt_ctx* c, const float camera[28], int n_frames, const float
                     const rt_present_params* present) {
     if (!c) return RT_ERR_INVALID_ARG;
     int r;
+    if ((r = moved_to_reprojected(c, camera, n_frames, rand_factors, reproject))) return r;
+    return moved_filter_present(c, denoise, guides, present);
+}
+
+}  // extern "C"
+
+namespace rt_impl {
+
+// rt_render_moved's steps 1 to 5
+int moved_to_reprojected(rt_ctx* c, const float camera[28], int n_frames, const float* rand_factors,
+                         const rt_reproject_params* reproject) {
+    int r;
     // a result made from the feature buffers now held, and those current: it is the pose's being left
     const bool result_here = c->rp_valid && c->ft_valid && c->rp_ft_gen == c->ft_gen;
     if ((r = rt_history_capture(c, result_here ? RT_HISTORY_FROM_REPROJECTED : RT_HISTORY_FROM_IMAGE))) return r;
     if ((r = rt_set_camera(c, camera))) return r;
     if ((r = rt_render(c, 1, n_frames, rand_factors))) return r;
     if ((r = rt_render_features(c))) return r;
-    if ((r = rt_reproject(c, reproject))) return r;
+    return rt_reproject(c, reproject);
+}
+
+// ... and its steps 6 and 7
+int moved_filter_present(rt_ctx* c, const rt_denoise_params* denoise, const rt_guide_params* guides,
+                         const rt_present_params* present) {
+    int r;
     if (c->hist_var && (r = rt_denoise_reprojected(c, denoise, guides))) return r;
     rt_present_params p;
     if (present) {
@@ -262,4 +281,4 @@ int rt_render_moved(rt_ctx* c, const float camera[28], int n_frames, const float
     return rt_present(c, &p);
 }
 
-}  // extern "C"
+}  // namespace rt_impl

@@ -46,6 +46,10 @@
 // pose through rt_render_moved: history kept, the new view rendered, reprojected, filtered and presented on
 // the device.  Each pose's frame (rt_read_presented, alpha dropped) is saved as <output stem>.moveNN.png.
 // The frames of pose k (1-based) take the factors of frame indices spp + (k - 1) * N onwards.  One device; needs -o.
+// --move-refine <K> spends K more frames per pose on the 8x8 tiles the history does not reach
+// (rt_render_moved_refined); --move-refine-count <C> names the count below which a pixel is short (default
+// N + K) and --move-refine-tiles <M> caps the tiles refined per pose.  Pose k then takes the factors of frame
+// indices spp + (k - 1) * (N + K) onwards, N for the pose and K for the refinement.
 #include "rt/rt.h"
 #include "rt/rt_scene.h"
 
@@ -71,7 +75,7 @@ struct Opt {
 };
 
 // commons-cli Options in Main.getOptions order (Main.java:43-70)
-enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_DENOISE, O_DENOISE_LEVELS, O_DENOISE_K, O_RAW_OUT, O_DENOISE_GUIDES, O_DENOISE_KN, O_DENOISE_KZ, O_DENOISE_KA, O_FEATURES_OUT, O_MOVES, O_MOVE_SHIFT, O_MOVE_FRAMES, O_N };
+enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_DENOISE, O_DENOISE_LEVELS, O_DENOISE_K, O_RAW_OUT, O_DENOISE_GUIDES, O_DENOISE_KN, O_DENOISE_KZ, O_DENOISE_KA, O_FEATURES_OUT, O_MOVES, O_MOVE_SHIFT, O_MOVE_FRAMES, O_MOVE_REFINE, O_MOVE_REFINE_COUNT, O_MOVE_REFINE_TILES, O_N };
 const Opt kOpts[O_N] = {
     {"h", "help", false, "print help message"},
     {"s", "scene", true, "scene ID"},
@@ -100,6 +104,9 @@ const Opt kOpts[O_N] = {
     {nullptr, "moves", true, "after the render: this many camera poses, each saved as <output stem>.moveNN.png"},
     {nullptr, "move-shift", true, "with --moves: viewport widths each pose moves sideways from the one before"},
     {nullptr, "move-frames", true, "with --moves: frames rendered at each pose (reprojected, filtered, presented)"},
+    {nullptr, "move-refine", true, "with --moves: extra frames per pose on the 8x8 tiles the history does not reach"},
+    {nullptr, "move-refine-count", true, "with --move-refine: a pixel is short below this count (default: the frames a refined tile gets)"},
+    {nullptr, "move-refine-tiles", true, "with --move-refine: at most this many tiles refined per pose (default: no cap)"},
 };
 
 // HelpFormatter.printHelp("OpenGL Ray Tracer", options): options sorted by key.
@@ -312,9 +319,13 @@ int main(int argc, char** argv) {
         die("rtrender", "--features-output renders on one device (--devices names more)");
 
     const bool moving = seen[O_MOVES];
-    int moves = 0, move_frames = 0;
-    float move_shift = 0.0f;
+    int moves = 0, move_frames = 0, move_refine = 0, move_refine_tiles = 0;
+    float move_shift = 0.0f, move_refine_count = 0.0f;
     if (!moving && (seen[O_MOVE_SHIFT] || seen[O_MOVE_FRAMES])) die("rtrender", "--move-shift and --move-frames go with --moves");
+    if (!moving && (seen[O_MOVE_REFINE] || seen[O_MOVE_REFINE_COUNT] || seen[O_MOVE_REFINE_TILES]))
+        die("rtrender", "--move-refine, --move-refine-count and --move-refine-tiles go with --moves");
+    if (!seen[O_MOVE_REFINE] && (seen[O_MOVE_REFINE_COUNT] || seen[O_MOVE_REFINE_TILES]))
+        die("rtrender", "--move-refine-count and --move-refine-tiles go with --move-refine");
     if (moving) {
         if (!seen[O_MOVE_SHIFT] || !seen[O_MOVE_FRAMES])
             die("rtrender", "--moves needs --move-shift <S> and --move-frames <N>");
@@ -328,6 +339,20 @@ int main(int argc, char** argv) {
             die("rtrender", "--move-shift must be a finite number");
         if (devices.size() > 1) die("rtrender", "--moves renders on one device (--devices names more)");
         if (output.empty()) die("rtrender", "--moves needs -o <png> (the poses are saved beside it)");
+        if (seen[O_MOVE_REFINE]) {
+            move_refine = parse_int(val[O_MOVE_REFINE]);
+            if (move_refine < 1) die("rtrender", "--move-refine must be at least 1");
+            if (move_refine > INT_MAX - move_frames) die("rtrender", "--move-refine is too large");
+        }
+        if (seen[O_MOVE_REFINE_COUNT]) {
+            move_refine_count = std::strtof(val[O_MOVE_REFINE_COUNT].c_str(), &end);
+            if (val[O_MOVE_REFINE_COUNT].empty() || *end != '\0' || !(move_refine_count > 0.0f) || !(move_refine_count <= 3.0e38f))
+                die("rtrender", "--move-refine-count must be a finite number > 0");
+        }
+        if (seen[O_MOVE_REFINE_TILES]) {
+            move_refine_tiles = parse_int(val[O_MOVE_REFINE_TILES]);
+            if (move_refine_tiles < 1) die("rtrender", "--move-refine-tiles must be at least 1");
+        }
     }
 
     rts_scene* scene = nullptr;
@@ -506,7 +531,15 @@ int main(int argc, char** argv) {
         const size_t dot = output.rfind('.');
         const bool has_ext = dot != std::string::npos && output.find('/', dot) == std::string::npos && dot > 0;
         const std::string stem = has_ext ? output.substr(0, dot) : output;
-        std::vector<float> mrf((size_t)move_frames);
+        const int pose_frames = move_frames + move_refine;   // the pose's own, then the refinement's
+        std::vector<float> mrf((size_t)pose_frames);
+        rt_refine_params refine;
+        std::memset(&refine, 0, sizeof(refine));
+        refine.min_count = move_refine_count;
+        refine.extra_frames = move_refine;
+        refine.max_tiles = move_refine_tiles;
+        int n_tiles = 0;
+        if (move_refine) chk(rt_read_tile_frames(ctx, nullptr, 0, &n_tiles), "rt_read_tile_frames");
         std::vector<uint8_t> rgba8(n * 4), rgb8(n * 3);
         const float step = (float)((double)move_shift * width);
         for (int k = 1; k <= moves; k++) {
@@ -515,9 +548,14 @@ int main(int argc, char** argv) {
                 ubo[4 + c] += v;
                 ubo[8 + c] += v;
             }
-            for (int i = 0; i < move_frames; i++)
-                mrf[(size_t)i] = rt_frame_rand_factor((uint64_t)seed, (uint64_t)spp + (uint64_t)(k - 1) * move_frames + i);
-            chk(rt_render_moved(ctx, ubo, move_frames, mrf.data(), nullptr, nullptr, nullptr, nullptr), "rt_render_moved");
+            for (int i = 0; i < pose_frames; i++)
+                mrf[(size_t)i] = rt_frame_rand_factor((uint64_t)seed, (uint64_t)spp + (uint64_t)(k - 1) * pose_frames + i);
+            int refined = 0;
+            if (move_refine)
+                chk(rt_render_moved_refined(ctx, ubo, move_frames, mrf.data(), &refine, nullptr, nullptr, nullptr, nullptr, &refined),
+                    "rt_render_moved_refined");
+            else
+                chk(rt_render_moved(ctx, ubo, move_frames, mrf.data(), nullptr, nullptr, nullptr, nullptr), "rt_render_moved");
             chk(rt_read_presented(ctx, rgba8.data()), "rt_read_presented");
             for (size_t i = 0; i < n; i++)
                 for (int c = 0; c < 3; c++) rgb8[i * 3 + c] = rgba8[i * 4 + c];
@@ -528,7 +566,11 @@ int main(int argc, char** argv) {
                 uncaught("java.lang.RuntimeException", "Failed to save texture as PNG");
             char abs_path[PATH_MAX];
             const char* shown = realpath(name.c_str(), abs_path) ? abs_path : name.c_str();
-            std::printf("Move %d/%d: %d frame(s), saved to: %s\n", k, moves, move_frames, shown);
+            if (move_refine)
+                std::printf("Move %d/%d: %d frame(s), +%d on %d of %d tiles, saved to: %s\n", k, moves, move_frames, move_refine,
+                            refined, n_tiles, shown);
+            else
+                std::printf("Move %d/%d: %d frame(s), saved to: %s\n", k, moves, move_frames, shown);
         }
     }
     rt_destroy(ctx);

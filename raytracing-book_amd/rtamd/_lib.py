@@ -101,6 +101,18 @@ class RtPresentParams(ctypes.Structure):
                 ("reserved", ctypes.c_int * 5)]
 
 
+class RtTileReach(ctypes.Structure):
+    """rt.h rt_tile_reach (numpy: TILE_REACH_DTYPE)."""
+    _fields_ = [("n_min", ctypes.c_float), ("n_sum", ctypes.c_float), ("short_px", ctypes.c_uint32),
+                ("pixels", ctypes.c_uint32)]
+
+
+class RtRefineParams(ctypes.Structure):
+    """rt.h rt_refine_params."""
+    _fields_ = [("min_count", ctypes.c_float), ("extra_frames", ctypes.c_int), ("min_pixels", ctypes.c_int),
+                ("max_tiles", ctypes.c_int), ("reserved", ctypes.c_int * 4)]
+
+
 RT_FEATURE_MISS = 0xFFFFFFFF   # rt.h
 
 RT_PK_N = 33   # rt_debug.h RT_PK_N
@@ -191,6 +203,15 @@ def _amd_protos(L, old_rev=False):
         _proto(L, "rt_bind_device_present", i, vp, vp, sz)
         _proto(L, "rt_present_host", i, c_float_p, c_float_p, c_float_p, i32_p, i, i, i, pp_p, u8_p, c_float_p)
         _proto(L, "rt_render_moved", i, vp, c_float_p, i, c_float_p, rp_p, dp_p, gp_p, pp_p)
+    if not old_rev or hasattr(L, "rt_reach_tiles"):   # ... or from before the reach records
+        dp_p, gp_p = ctypes.POINTER(RtDenoiseParams), ctypes.POINTER(RtGuideParams)
+        rp_p, pp_p = ctypes.POINTER(RtReprojectParams), ctypes.POINTER(RtPresentParams)
+        tr_p, rf_p, u8_p = ctypes.POINTER(RtTileReach), ctypes.POINTER(RtRefineParams), ctypes.POINTER(ctypes.c_uint8)
+        _proto(L, "rt_reach_tiles", i, vp, f)
+        _proto(L, "rt_read_tile_reach", i, vp, tr_p, i, c_int_p)
+        _proto(L, "rt_tile_reach_host", i, c_float_p, i, i, f, tr_p, i)
+        _proto(L, "rt_refine_select", i, tr_p, i, i, i, u8_p, c_int_p)
+        _proto(L, "rt_render_moved_refined", i, vp, c_float_p, i, c_float_p, rf_p, rp_p, dp_p, gp_p, pp_p, c_int_p)
     _proto(L, "rt_abi_version", i)
     _proto(L, "rt_create", i, i, c_int_p, ctypes.POINTER(vp))
     _proto(L, "rt_destroy", i, vp)

@@ -488,6 +488,54 @@ def present_host(source="image", image=None, denoised=None, reprojected=None, ti
     return (out, flt) if keep_float else out
 
 
+TILE_REACH_DTYPE = np.dtype([("n_min", "<f4"), ("n_sum", "<f4"), ("short_px", "<u4"), ("pixels", "<u4")])   # rt.h rt_tile_reach
+
+
+def tile_reach_host(rgbn, min_count, lib=None):
+    """rt_tile_reach_host (host only, no device): one TILE_REACH_DTYPE record per 8x8 tile (row-major) of a
+    reprojected result [H, W, 4] float32 (r, g, b, n_out): the smallest and the summed good count, the pixels
+    whose count is short of min_count, the pixels in the image."""
+    L = lib or _lib.amd()
+    r = np.ascontiguousarray(rgbn, dtype=np.float32)
+    if r.ndim != 3 or r.shape[2] != 4:
+        raise ValueError("rgbn is [H, W, 4]")
+    H, W = r.shape[:2]
+    out = np.zeros(((W + 7) // 8) * ((H + 7) // 8), dtype=TILE_REACH_DTYPE)
+    rc = L.rt_tile_reach_host(r.ctypes.data_as(c_float_p), W, H, float(min_count),
+                              out.ctypes.data_as(ctypes.POINTER(_lib.RtTileReach)), int(out.size))
+    if rc != 0:
+        raise RTError(rc, "rt_tile_reach_host: min_count > 0 and finite required")
+    return out
+
+
+def refine_select(reach, min_pixels=1, max_tiles=0, lib=None):
+    """rt_refine_select (host only, pure): the tiles with short_px >= min_pixels -> uint8 array, one per tile.
+    max_tiles > 0: the threshold rises until at most that many remain; equal counts stay or go together, so
+    fewer may be chosen, and none when every tile is entirely fresh."""
+    L = lib or _lib.amd()
+    t = np.ascontiguousarray(reach, dtype=TILE_REACH_DTYPE)
+    out = np.zeros(t.size, np.uint8)
+    n = ctypes.c_int()
+    rc = L.rt_refine_select(t.ctypes.data_as(ctypes.POINTER(_lib.RtTileReach)), int(t.size), int(min_pixels),
+                            int(max_tiles), out.ctypes.data_as(ctypes.POINTER(ctypes.c_uint8)), ctypes.byref(n))
+    if rc != 0:
+        raise RTError(rc, "rt_refine_select: min_pixels in 1 .. 64, max_tiles >= 0, every short_px <= 64 required")
+    return out
+
+
+def _refine_params(refine):
+    """rt_refine_params for a dict of extra_frames, min_count, min_pixels, max_tiles (missing keys: 0)."""
+    unknown = set(refine) - {"extra_frames", "min_count", "min_pixels", "max_tiles"}
+    if unknown:
+        raise ValueError(f"refine: unknown keys {sorted(unknown)}")
+    p = _lib.RtRefineParams()
+    p.min_count = float(refine.get("min_count") or 0.0)
+    p.extra_frames = int(refine.get("extra_frames") or 0)
+    p.min_pixels = int(refine.get("min_pixels") or 0)
+    p.max_tiles = int(refine.get("max_tiles") or 0)
+    return p
+
+
 SHAPES = {0: "fast-lds", 1: "fast-global", 2: "link-lds", 3: "meta-lds", 4: "meta-global", 5: "link-two-level"}
 
 
@@ -829,13 +877,30 @@ class RenderContext:
         data_ptr() of at least H * W * 4 bytes), on the context's stream; None / 0 returns to the internal buffer."""
         self._check(self._L.rt_bind_device_present(self._h, ctypes.c_void_p(ptr or None), ctypes.c_size_t(nbytes)))
 
+    # -- extra frames where the history does not reach (rt.h rt_reach_tiles / rt_render_moved_refined)
+    def reach_tiles(self, min_count):
+        """rt_reach_tiles: queue the reduction of the held reproject() result's counts to one record per 8x8
+        tile; a pixel is short when its count is below min_count."""
+        self._check(self._L.rt_reach_tiles(self._h, float(min_count)))
+
+    def read_tile_reach(self):
+        """rt_read_tile_reach: one TILE_REACH_DTYPE record per 8x8 tile, row-major."""
+        n = ctypes.c_int()
+        self._check(self._L.rt_read_tile_reach(self._h, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, dtype=TILE_REACH_DTYPE)
+        self._check(self._L.rt_read_tile_reach(self._h, out.ctypes.data_as(ctypes.POINTER(_lib.RtTileReach)), n.value,
+                                               ctypes.byref(n)))
+        return out
+
     def render_moved(self, camera, rand_factors, source=None, exposure=1.0, keep_float=False, cos_min=None, kz=None,
-                     max_history=None, levels=None, k=None, guides=True):
+                     max_history=None, levels=None, k=None, guides=True, refine=None):
         """rt_render_moved + rt_read_presented: one pose of a moving camera -> [H, W, 4] uint8.  Captures the
         history, moves to `camera` (28 floats), renders len(rand_factors) frames from frame 1 and the features,
         reprojects, filters (under set_history_variance()) and presents.  source None: the library's choice
         ("moved" under set_history_variance(), else "reprojected") unless exposure or keep_float ask for
-        parameters, then the same choice made here.  The other arguments are reproject()'s and denoise_reprojected()'s."""
+        parameters, then the same choice made here.  The other arguments are reproject()'s and denoise_reprojected()'s.
+        refine: a dict of extra_frames and optionally min_count, min_pixels, max_tiles = rt_render_moved_refined ->
+        (frame, tiles refined): the last extra_frames of rand_factors go to the tiles the history does not reach."""
         cam = np.ascontiguousarray(camera, dtype=np.float32).ravel()
         assert cam.size == 28
         rf = np.ascontiguousarray(rand_factors, dtype=np.float32)
@@ -845,6 +910,17 @@ class RenderContext:
             src = source if source is not None else ("moved" if getattr(self, "_history_variance", False) else "reprojected")
             pp = _present_params(src, exposure, keep_float)
         g = (0.0, 0.0, 0.0) if guides is None or guides is False else guides
+        if refine is not None:
+            rp = _refine_params(refine)
+            n = int(rf.size) - max(rp.extra_frames, 0)
+            if n < 1:
+                raise ValueError("rand_factors holds the pose's frames and then extra_frames more")
+            tiles = ctypes.c_int()
+            self._check(self._L.rt_render_moved_refined(self._h, cam.ctypes.data_as(c_float_p), n, rf.ctypes.data_as(c_float_p),
+                                                        ctypes.byref(rp), _reproject_params(cos_min, kz, max_history),
+                                                        _denoise_params(levels, k), _guide_params(g), pp,
+                                                        ctypes.byref(tiles)))
+            return self.read_presented(), tiles.value
         self._check(self._L.rt_render_moved(self._h, cam.ctypes.data_as(c_float_p), int(rf.size), rf.ctypes.data_as(c_float_p),
                                             _reproject_params(cos_min, kz, max_history), _denoise_params(levels, k),
                                             _guide_params(g), pp))
