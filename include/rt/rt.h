@@ -540,6 +540,41 @@ int rt_denoise_reprojected_host(const float* rgbn, const float* s2, const float*
                                 int width, int height, const rt_denoise_params* params, const rt_guide_params* guides,
                                 float* rgba_out);
 
+/* ---- Misses reprojected by direction --------------------------------------------------------------------
+ * rt_reproject's step 1 leaves a pixel whose centre ray hits nothing with its own one or two frames.  The
+ * first-hit pass leaves the constant media out, so such a pixel is the background seen through whatever fog
+ * the scene has: often the noisiest part of the picture.  With rt_set_reproject_misses(ctx, 1) a miss is
+ * reprojected too, as the point at infinity along its ray.  The arithmetic is the definition's: f32, no
+ * contraction, the same operation set.  For a pixel p that is guide-good and a miss (id == RT_FEATURE_MISS):
+ *   2m. d as in step 2;  w = d.  No P is formed and t is not read.
+ *   3.  Unchanged, applied to that w: a, b, c from M; reject unless c > 0; fx = a / c, fy = b / c; the same
+ *       window test, floor and weights.
+ *   4m. A tap q is accepted when it is inside the image, n_h(q) > 0, q's history features are guide-good and
+ *       a miss, and the bits of its albedo word's x, y, z (the background the miss was rendered under) equal
+ *       those of p's.  There is no cos_min and no kz test.  The sums, and rt_set_history_variance's, are step 4's.
+ *   5, 6. Unchanged, the variance blend included.
+ * A miss has no surface: what p sees along d is what the old view saw along the same direction, so the
+ * background's bits are the miss's id test -- they reject history taken under another rt_set_params background
+ * -- and "q is a miss" is its disocclusion test.  A hit pixel's word and s2 are bit for bit what they are with
+ * the switch off: it never accepts a miss tap (its id differs), and a miss never accepts a hit tap.  What the
+ * history holds beyond the background itself is radiance gathered for the old camera position (fog in-scatter:
+ * the "known lag" of a view-dependent surface, bounded by max_history); the defocus disk is ignored, as in the
+ * first-hit pass; at a silhouette a miss tap's history may hold some object colour from the frames' jitter.
+ *
+ * Off is the default: rt_reproject launches the kernels it launches without this call and gives the same
+ * bits.  Changing the value drops the held result (RT_ERR_STATE from rt_present, rt_reach_tiles,
+ * rt_denoise_reprojected, rt_read_reprojected and RT_HISTORY_FROM_REPROJECTED until the next rt_reproject) and
+ * keeps the history, which is the same under both values.  It allocates nothing.  rt_render_moved's and
+ * rt_render_moved_refined's rt_reproject steps obey it. */
+int rt_set_reproject_misses(rt_ctx* ctx, int on);
+/* Host only, no device: rt_reproject_host (history_s2, m2 and s2_out all NULL) or rt_reproject_variance_host
+ * (all three given; any other mix is RT_ERR_INVALID_ARG) with the misses reprojected by direction. */
+int rt_reproject_misses_host(const float* history_rgbn, const float* history_nd, const float* history_ai,
+                             const float* history_s2, const float history_camera[28], const float* image,
+                             const float* m2, const int32_t* tile_frames, int n_tiles, const float* normal_depth,
+                             const float* albedo_id, const float camera[28], int width, int height,
+                             const rt_reproject_params* params, float* rgbn_out, float* s2_out);
+
 /* ---- The presented frame: compose, expose and tonemap on the device ----------------------------------
  * The display path of the reference (Texture.saveAsPNG: float -> unorm8 -> gamma table, what
  * rts_tonemap_rgb8 does on the host) as one kernel over a buffer the context holds, so a preview leaves the

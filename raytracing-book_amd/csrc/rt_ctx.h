@@ -117,6 +117,9 @@ struct rt_ctx : rt_impl::SceneState {
     // feature buffers the held result was made from (rt_denoise_reprojected filters over the same ones)
     bool hist_var = false;
     uint32_t rp_ft_gen = 0;
+    // rt_set_reproject_misses: rt_reproject launches the instances that reproject misses by direction; a held
+    // result was made under the current value (a change drops it and keeps the history)
+    bool rp_misses = false;
     // rp_gen counts the rt_reproject results made (the held one is the rp_gen-th); dn_rp_gen: the rp_gen of the
     // result rt_denoise_reprojected wrote the denoised buffer from, 0 when another filter call wrote it or none did
     uint32_t rp_gen = 0, dn_rp_gen = 0;

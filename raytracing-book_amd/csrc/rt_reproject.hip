@@ -16,6 +16,10 @@
 // reproject_var_kernel, which carry the per-sample variance s2 of y beside the pixel: one more float read
 // per pixel (M2.w) and per tap (the history's s2, in the cache line of a neighbouring lane's), one more
 // written.  With the switch off the two kernels above are the ones launched, with nothing else allocated.
+//
+// rt_set_reproject_misses(ctx, 1) switches rt_reproject to reproject_miss_kernel / reproject_miss_var_kernel, the
+// same body with rp_pixel_t's MISS on: a pixel that hits nothing is gathered by its ray's direction from the
+// history's misses under the same background.  Off, the kernels above run as they always did.
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
@@ -88,6 +92,33 @@ __global__ void __launch_bounds__(256) reproject_var_kernel(const rt_dn4* __rest
     const size_t p = (size_t)y * V.W + x;
     float s2;
     dst[p] = rp_pixel_var(image[p], counts[tile], nd[p], ai[p], hc, hnd, hai, V, x, y, moments[p].w, hs2, &s2);
+    dst_s2[p] = s2;
+}
+
+// rt_set_reproject_misses: the two gathers above with the misses reprojected by direction.  The same launch
+// shape and the same reads; a miss lane skips the point and the depth test and compares the background's bits.
+__global__ void __launch_bounds__(256) reproject_miss_kernel(const rt_dn4* __restrict__ image, const int32_t* __restrict__ counts,
+                                                             const rt_dn4* __restrict__ nd, const rt_dn4* __restrict__ ai,
+                                                             const rt_dn4* __restrict__ hc, const rt_dn4* __restrict__ hnd,
+                                                             const rt_dn4* __restrict__ hai, rt_rp_view V,
+                                                             rt_dn4* __restrict__ dst) {
+    int x, y, tile;
+    if (!tile_pixel(V.W, V.H, x, y, tile)) return;
+    const size_t p = (size_t)y * V.W + x;
+    dst[p] = rp_pixel_miss(image[p], counts[tile], nd[p], ai[p], hc, hnd, hai, V, x, y);
+}
+
+__global__ void __launch_bounds__(256) reproject_miss_var_kernel(const rt_dn4* __restrict__ image, const rt_dn4* __restrict__ moments,
+                                                                 const int32_t* __restrict__ counts, const rt_dn4* __restrict__ nd,
+                                                                 const rt_dn4* __restrict__ ai, const rt_dn4* __restrict__ hc,
+                                                                 const rt_dn4* __restrict__ hnd, const rt_dn4* __restrict__ hai,
+                                                                 const float* __restrict__ hs2, rt_rp_view V,
+                                                                 rt_dn4* __restrict__ dst, float* __restrict__ dst_s2) {
+    int x, y, tile;
+    if (!tile_pixel(V.W, V.H, x, y, tile)) return;
+    const size_t p = (size_t)y * V.W + x;
+    float s2;
+    dst[p] = rp_pixel_miss_var(image[p], counts[tile], nd[p], ai[p], hc, hnd, hai, V, x, y, moments[p].w, hs2, &s2);
     dst_s2[p] = s2;
 }
 
@@ -246,15 +277,16 @@ int rt_reproject(rt_ctx* c, const rt_reproject_params* params) {
     V.H = H;
     const dim3 grid((unsigned)((nt + kTilesPerBlock - 1) / kTilesPerBlock));
     if (c->hist_var)
-        hipLaunchKernelGGL(reproject_var_kernel, grid, dim3(256), 0, d.stream, (const rt_dn4*)d.image_ptr, (const rt_dn4*)d.m2.ptr,
-                           (const int32_t*)d.rp_counts.ptr, (const rt_dn4*)d.ft_nd.ptr, (const rt_dn4*)d.ft_ai.ptr,
-                           (const rt_dn4*)d.hs_px.ptr, (const rt_dn4*)d.hs_nd.ptr, (const rt_dn4*)d.hs_ai.ptr,
-                           (const float*)d.hs_s2.ptr, V, (rt_dn4*)d.rp_out.ptr, (float*)d.rp_s2.ptr);
+        hipLaunchKernelGGL(c->rp_misses ? reproject_miss_var_kernel : reproject_var_kernel, grid, dim3(256), 0, d.stream,
+                           (const rt_dn4*)d.image_ptr, (const rt_dn4*)d.m2.ptr, (const int32_t*)d.rp_counts.ptr,
+                           (const rt_dn4*)d.ft_nd.ptr, (const rt_dn4*)d.ft_ai.ptr, (const rt_dn4*)d.hs_px.ptr,
+                           (const rt_dn4*)d.hs_nd.ptr, (const rt_dn4*)d.hs_ai.ptr, (const float*)d.hs_s2.ptr, V,
+                           (rt_dn4*)d.rp_out.ptr, (float*)d.rp_s2.ptr);
     else
-        hipLaunchKernelGGL(reproject_kernel, grid, dim3(256), 0, d.stream, (const rt_dn4*)d.image_ptr,
-                           (const int32_t*)d.rp_counts.ptr, (const rt_dn4*)d.ft_nd.ptr, (const rt_dn4*)d.ft_ai.ptr,
-                           (const rt_dn4*)d.hs_px.ptr, (const rt_dn4*)d.hs_nd.ptr, (const rt_dn4*)d.hs_ai.ptr, V,
-                           (rt_dn4*)d.rp_out.ptr);
+        hipLaunchKernelGGL(c->rp_misses ? reproject_miss_kernel : reproject_kernel, grid, dim3(256), 0, d.stream,
+                           (const rt_dn4*)d.image_ptr, (const int32_t*)d.rp_counts.ptr, (const rt_dn4*)d.ft_nd.ptr,
+                           (const rt_dn4*)d.ft_ai.ptr, (const rt_dn4*)d.hs_px.ptr, (const rt_dn4*)d.hs_nd.ptr,
+                           (const rt_dn4*)d.hs_ai.ptr, V, (rt_dn4*)d.rp_out.ptr);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return set_err(c, RT_ERR_DEVICE, std::string("rt_reproject launch failed: ") + hipGetErrorString(e));
     c->rp_ft_gen = c->ft_gen;
@@ -279,6 +311,14 @@ int rt_set_history_variance(rt_ctx* c, int on) {
     if ((on != 0) == c->hist_var) return RT_OK;
     c->hist_var = on != 0;
     c->hs_valid = c->rp_valid = false;   // what is held was made under the other value
+    return RT_OK;
+}
+
+int rt_set_reproject_misses(rt_ctx* c, int on) {
+    if (!c) return RT_ERR_INVALID_ARG;
+    if ((on != 0) == c->rp_misses) return RT_OK;
+    c->rp_misses = on != 0;
+    c->rp_valid = false;   // the result was made under the other value; the history is the same under both
     return RT_OK;
 }
 

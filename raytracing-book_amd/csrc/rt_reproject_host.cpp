@@ -1,7 +1,7 @@
 // rt_reproject_host.cpp — the host half of temporal reprojection (rt.h rt_reproject): the parameter
 // resolve and the history view's matrix that rt_history_capture and rt_reproject share with the host
-// reference, and rt_reproject_host, rt_reproject_variance_host and rt_history_variance_host, rt_reproject_math.h's
-// functions over caller arrays.  Plain C++, no device.
+// reference, and rt_reproject_host, rt_reproject_variance_host, rt_reproject_misses_host and
+// rt_history_variance_host, rt_reproject_math.h's functions over caller arrays.  Plain C++, no device.
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -54,7 +54,9 @@ int reproject_matrix(const rt_camera_ubo& cam, float M[9]) {
 
 namespace {
 
-// rt_reproject_host (history_s2, m2, s2_out NULL) and rt_reproject_variance_host over caller arrays
+// rt_reproject_host (history_s2, m2, s2_out NULL) and rt_reproject_variance_host over caller arrays;
+// MISS: rt_reproject_misses_host, the same loop over rp_pixel_t<VAR, true>
+template <bool MISS>
 int reproject_host(const float* history_rgbn, const float* history_nd, const float* history_ai, const float* history_s2,
                    const float history_camera[28], const float* image, const float* m2, const int32_t* tile_frames, int n_tiles,
                    const float* normal_depth, const float* albedo_id, const float camera[28], int width, int height,
@@ -100,10 +102,12 @@ int reproject_host(const float* history_rgbn, const float* history_nd, const flo
                 rt_dn4 o;
                 if (s2_out) {
                     float s2;
-                    o = rp_pixel_var(img, count, nd, ai, hc.data(), hnd.data(), hai.data(), V, x, y, m2[p * 4 + 3], hs2.data(), &s2);
+                    o = rp_pixel_t<true, MISS>(img, count, nd, ai, hc.data(), hnd.data(), hai.data(), V, x, y, m2[p * 4 + 3],
+                                               hs2.data(), &s2);
                     s2_out[p] = s2;
                 } else {
-                    o = rp_pixel(img, count, nd, ai, hc.data(), hnd.data(), hai.data(), V, x, y);
+                    o = rp_pixel_t<false, MISS>(img, count, nd, ai, hc.data(), hnd.data(), hai.data(), V, x, y, 0.0f, nullptr,
+                                                nullptr);
                 }
                 std::memcpy(rgbn_out + p * 4, &o, sizeof(o));
             }
@@ -119,7 +123,7 @@ extern "C" int rt_reproject_host(const float* history_rgbn, const float* history
                                  const float history_camera[28], const float* image, const int32_t* tile_frames, int n_tiles,
                                  const float* normal_depth, const float* albedo_id, const float camera[28], int width,
                                  int height, const rt_reproject_params* params, float* rgbn_out) {
-    return reproject_host(history_rgbn, history_nd, history_ai, nullptr, history_camera, image, nullptr, tile_frames, n_tiles,
+    return reproject_host<false>(history_rgbn, history_nd, history_ai, nullptr, history_camera, image, nullptr, tile_frames, n_tiles,
                           normal_depth, albedo_id, camera, width, height, params, rgbn_out, nullptr);
 }
 
@@ -129,8 +133,19 @@ extern "C" int rt_reproject_variance_host(const float* history_rgbn, const float
                                           const float* albedo_id, const float camera[28], int width, int height,
                                           const rt_reproject_params* params, float* rgbn_out, float* s2_out) {
     if (!history_s2 || !m2 || !s2_out) return RT_ERR_INVALID_ARG;
-    return reproject_host(history_rgbn, history_nd, history_ai, history_s2, history_camera, image, m2, tile_frames, n_tiles,
+    return reproject_host<false>(history_rgbn, history_nd, history_ai, history_s2, history_camera, image, m2, tile_frames, n_tiles,
                           normal_depth, albedo_id, camera, width, height, params, rgbn_out, s2_out);
+}
+
+extern "C" int rt_reproject_misses_host(const float* history_rgbn, const float* history_nd, const float* history_ai,
+                                        const float* history_s2, const float history_camera[28], const float* image,
+                                        const float* m2, const int32_t* tile_frames, int n_tiles, const float* normal_depth,
+                                        const float* albedo_id, const float camera[28], int width, int height,
+                                        const rt_reproject_params* params, float* rgbn_out, float* s2_out) {
+    const int given = (history_s2 != nullptr) + (m2 != nullptr) + (s2_out != nullptr);
+    if (given != 0 && given != 3) return RT_ERR_INVALID_ARG;
+    return reproject_host<true>(history_rgbn, history_nd, history_ai, history_s2, history_camera, image, m2, tile_frames, n_tiles,
+                                normal_depth, albedo_id, camera, width, height, params, rgbn_out, s2_out);
 }
 
 extern "C" int rt_history_variance_host(const float* image, const float* m2, const int32_t* tile_frames, int n_tiles, int width,

@@ -46,7 +46,10 @@ RT_HD float rp_history_s2(const rt_dn4 img, float m2w, int count) {
 // VAR: the variance is carried too (m2w the pixel's M2.w, hs2 the history's s2, one float per pixel; the
 // result's s2 goes to *s2_out).  The {r, g, b, n_out} word comes out of the same operations either way;
 // VAR = false compiles to rt_reproject as it was and touches none of the three.
-template <bool VAR>
+// MISS (rt.h rt_set_reproject_misses): a guide-good pixel whose centre ray hits nothing is reprojected by
+// its direction (steps 2m and 4m); a hit pixel's operations are the same under either value, and
+// MISS = false compiles to the code as it was.
+template <bool VAR, bool MISS = false>
 RT_HD rt_dn4 rp_pixel_t(const rt_dn4 img, int count, const rt_dn4 nd, const rt_dn4 ai, const rt_dn4* __restrict__ hc,
                         const rt_dn4* __restrict__ hnd, const rt_dn4* __restrict__ hai, const rt_rp_view& V, int x, int y,
                         float m2w, const float* __restrict__ hs2, float* __restrict__ s2_out) {
@@ -59,14 +62,19 @@ RT_HD rt_dn4 rp_pixel_t(const rt_dn4 img, int count, const rt_dn4 nd, const rt_d
         s2_c = rp_history_s2(img, m2w, count);
         *s2_out = s2_c;   // what every `return out` below leaves: not reprojected, or rejected
     }
-    // 1. a miss, or first-hit words that are not finite: nothing to reproject
-    if (!(dn_guide_good(nd, ai) && dn_guide_hit(ai))) return out;
+    // 1. first-hit words that are not finite, or (without MISS) a miss: nothing to reproject
+    if (!dn_guide_good(nd, ai)) return out;
+    const bool hit = dn_guide_hit(ai);
+    if (!MISS && !hit) return out;
     // 2. the world point the pixel's centre ray lands on
     const v3 o = ld3(V.cam.camera_pos), o_h = ld3(V.cam_h.camera_pos);
     const v3 d = sub3(rp_pixel_base(V.cam, (float)x, (float)y), o);
-    const v3 P = mk3(o.x + d.x * nd.w, o.y + d.y * nd.w, o.z + d.z * nd.w);
-    // 3. into the history view
-    const v3 w = sub3(P, o_h);
+    v3 w = d;   // 2m. a miss: the direction itself stands for the point at infinity
+    if (!MISS || hit) {
+        const v3 P = mk3(o.x + d.x * nd.w, o.y + d.y * nd.w, o.z + d.z * nd.w);
+        // 3. into the history view
+        w = sub3(P, o_h);
+    }
     const float a = (V.M[0] * w.x + V.M[1] * w.y) + V.M[2] * w.z;
     const float b = (V.M[3] * w.x + V.M[4] * w.y) + V.M[5] * w.z;
     const float c = (V.M[6] * w.x + V.M[7] * w.y) + V.M[8] * w.z;
@@ -89,12 +97,19 @@ RT_HD rt_dn4 rp_pixel_t(const rt_dn4 img, int count, const rt_dn4 nd, const rt_d
             const size_t q = (size_t)cy * W + cx;
             const rt_dn4 hq = hc[q], ndq = hnd[q], aiq = hai[q];
             const float u = (i ? ax : 1.0f - ax) * (j ? ay : 1.0f - ay);
-            bool use = in && hq.w > 0.0f && dn_guide_good(ndq, aiq) && dn_guide_hit(aiq) && rt_f2u(aiq.w) == rt_f2u(ai.w);
-            use = use && (nd.x * ndq.x + nd.y * ndq.y) + nd.z * ndq.z >= V.cos_min;
-            if (V.kz != 0.0f) {
-                const v3 dq = sub3(rp_pixel_base(V.cam_h, (float)cx, (float)cy), o_h);
-                const float t_exp = rp_dot(w, dq) / rp_dot(dq, dq);
-                use = use && fabsf(t_exp - ndq.w) <= V.kz * t_exp;
+            bool use = in && hq.w > 0.0f && dn_guide_good(ndq, aiq);
+            if (!MISS || hit) {
+                use = use && dn_guide_hit(aiq) && rt_f2u(aiq.w) == rt_f2u(ai.w);
+                use = use && (nd.x * ndq.x + nd.y * ndq.y) + nd.z * ndq.z >= V.cos_min;
+                if (V.kz != 0.0f) {
+                    const v3 dq = sub3(rp_pixel_base(V.cam_h, (float)cx, (float)cy), o_h);
+                    const float t_exp = rp_dot(w, dq) / rp_dot(dq, dq);
+                    use = use && fabsf(t_exp - ndq.w) <= V.kz * t_exp;
+                }
+            } else {
+                // 4m. a miss tap under p's background: the miss's id test; no cos_min and no kz test
+                use = use && !dn_guide_hit(aiq) && rt_f2u(aiq.x) == rt_f2u(ai.x) && rt_f2u(aiq.y) == rt_f2u(ai.y) &&
+                      rt_f2u(aiq.z) == rt_f2u(ai.z);
             }
             sw = use ? sw + u : sw;
             sr = use ? sr + u * hq.x : sr;
@@ -145,6 +160,16 @@ RT_HD rt_dn4 rp_pixel_var(const rt_dn4 img, int count, const rt_dn4 nd, const rt
                           const rt_dn4* __restrict__ hnd, const rt_dn4* __restrict__ hai, const rt_rp_view& V, int x, int y,
                           float m2w, const float* __restrict__ hs2, float* __restrict__ s2_out) {
     return rp_pixel_t<true>(img, count, nd, ai, hc, hnd, hai, V, x, y, m2w, hs2, s2_out);
+}
+// ... and with the misses reprojected by direction (rt_set_reproject_misses)
+RT_HD rt_dn4 rp_pixel_miss(const rt_dn4 img, int count, const rt_dn4 nd, const rt_dn4 ai, const rt_dn4* __restrict__ hc,
+                           const rt_dn4* __restrict__ hnd, const rt_dn4* __restrict__ hai, const rt_rp_view& V, int x, int y) {
+    return rp_pixel_t<false, true>(img, count, nd, ai, hc, hnd, hai, V, x, y, 0.0f, nullptr, nullptr);
+}
+RT_HD rt_dn4 rp_pixel_miss_var(const rt_dn4 img, int count, const rt_dn4 nd, const rt_dn4 ai, const rt_dn4* __restrict__ hc,
+                               const rt_dn4* __restrict__ hnd, const rt_dn4* __restrict__ hai, const rt_rp_view& V, int x, int y,
+                               float m2w, const float* __restrict__ hs2, float* __restrict__ s2_out) {
+    return rp_pixel_t<true, true>(img, count, nd, ai, hc, hnd, hai, V, x, y, m2w, hs2, s2_out);
 }
 
 // The parameters after defaults and checks (rt_reproject_host.cpp reproject_resolve).

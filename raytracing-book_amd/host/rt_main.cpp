@@ -50,6 +50,8 @@
 // (rt_render_moved_refined); --move-refine-count <C> names the count below which a pixel is short (default
 // N + K) and --move-refine-tiles <M> caps the tiles refined per pose.  Pose k then takes the factors of frame
 // indices spp + (k - 1) * (N + K) onwards, N for the pose and K for the refinement.
+// --move-misses reprojects the pixels whose centre ray hits nothing by the ray's direction too
+// (rt_set_reproject_misses): the background keeps its history, and fewer tiles qualify for --move-refine.
 #include "rt/rt.h"
 #include "rt/rt_scene.h"
 
@@ -75,7 +77,7 @@ struct Opt {
 };
 
 // commons-cli Options in Main.getOptions order (Main.java:43-70)
-enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_DENOISE, O_DENOISE_LEVELS, O_DENOISE_K, O_RAW_OUT, O_DENOISE_GUIDES, O_DENOISE_KN, O_DENOISE_KZ, O_DENOISE_KA, O_FEATURES_OUT, O_MOVES, O_MOVE_SHIFT, O_MOVE_FRAMES, O_MOVE_REFINE, O_MOVE_REFINE_COUNT, O_MOVE_REFINE_TILES, O_N };
+enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_DENOISE, O_DENOISE_LEVELS, O_DENOISE_K, O_RAW_OUT, O_DENOISE_GUIDES, O_DENOISE_KN, O_DENOISE_KZ, O_DENOISE_KA, O_FEATURES_OUT, O_MOVES, O_MOVE_SHIFT, O_MOVE_FRAMES, O_MOVE_REFINE, O_MOVE_REFINE_COUNT, O_MOVE_REFINE_TILES, O_MOVE_MISSES, O_N };
 const Opt kOpts[O_N] = {
     {"h", "help", false, "print help message"},
     {"s", "scene", true, "scene ID"},
@@ -107,6 +109,7 @@ const Opt kOpts[O_N] = {
     {nullptr, "move-refine", true, "with --moves: extra frames per pose on the 8x8 tiles the history does not reach"},
     {nullptr, "move-refine-count", true, "with --move-refine: a pixel is short below this count (default: the frames a refined tile gets)"},
     {nullptr, "move-refine-tiles", true, "with --move-refine: at most this many tiles refined per pose (default: no cap)"},
+    {nullptr, "move-misses", false, "with --moves: reproject the background (pixels that hit nothing) by ray direction too"},
 };
 
 // HelpFormatter.printHelp("OpenGL Ray Tracer", options): options sorted by key.
@@ -324,6 +327,7 @@ int main(int argc, char** argv) {
     if (!moving && (seen[O_MOVE_SHIFT] || seen[O_MOVE_FRAMES])) die("rtrender", "--move-shift and --move-frames go with --moves");
     if (!moving && (seen[O_MOVE_REFINE] || seen[O_MOVE_REFINE_COUNT] || seen[O_MOVE_REFINE_TILES]))
         die("rtrender", "--move-refine, --move-refine-count and --move-refine-tiles go with --moves");
+    if (!moving && seen[O_MOVE_MISSES]) die("rtrender", "--move-misses goes with --moves");
     if (!seen[O_MOVE_REFINE] && (seen[O_MOVE_REFINE_COUNT] || seen[O_MOVE_REFINE_TILES]))
         die("rtrender", "--move-refine-count and --move-refine-tiles go with --move-refine");
     if (moving) {
@@ -388,6 +392,7 @@ int main(int argc, char** argv) {
     chk(rt_resize(ctx, width, height), "rt_resize");
     if (denoise || moving) chk(rt_set_moments(ctx, 1), "rt_set_moments");
     if (moving) chk(rt_set_history_variance(ctx, 1), "rt_set_history_variance");
+    if (seen[O_MOVE_MISSES]) chk(rt_set_reproject_misses(ctx, 1), "rt_set_reproject_misses");
     // the first-hit pass, once: the scene and the camera do not change from here on
     // (with --moves the scene and the first pose's camera: rt_render_moved renders each later pose's)
     if (guides || !features_output.empty() || moving) chk(rt_render_features(ctx), "rt_render_features");

@@ -212,6 +212,11 @@ def _amd_protos(L, old_rev=False):
         _proto(L, "rt_tile_reach_host", i, c_float_p, i, i, f, tr_p, i)
         _proto(L, "rt_refine_select", i, tr_p, i, i, i, u8_p, c_int_p)
         _proto(L, "rt_render_moved_refined", i, vp, c_float_p, i, c_float_p, rf_p, rp_p, dp_p, gp_p, pp_p, c_int_p)
+    if not old_rev or hasattr(L, "rt_set_reproject_misses"):   # ... or from before the misses reprojected by direction
+        rp_p, i32_p = ctypes.POINTER(RtReprojectParams), ctypes.POINTER(ctypes.c_int32)
+        _proto(L, "rt_set_reproject_misses", i, vp, i)
+        _proto(L, "rt_reproject_misses_host", i, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
+               i32_p, i, c_float_p, c_float_p, c_float_p, i, i, rp_p, c_float_p, c_float_p)
     _proto(L, "rt_abi_version", i)
     _proto(L, "rt_create", i, i, c_int_p, ctypes.POINTER(vp))
     _proto(L, "rt_destroy", i, vp)

@@ -341,10 +341,11 @@ def history_from_image(image, tile_frames):
 
 
 def reproject_host(history, history_nd, history_ai, history_camera, image, tile_frames, normal_depth, albedo_id, camera,
-                   cos_min=None, kz=None, max_history=None, lib=None):
+                   cos_min=None, kz=None, max_history=None, lib=None, misses=False):
     """rt_reproject_host (host only, no device): the history (r, g, b, n), its first-hit buffers and 28-float
     camera block; the current image, one frame count per 8x8 tile (row-major; a scalar stands for every tile),
-    first-hit buffers and camera block -> [H, W, 4] float32 (r, g, b, n_out).  All buffers are [H, W, 4]."""
+    first-hit buffers and camera block -> [H, W, 4] float32 (r, g, b, n_out).  All buffers are [H, W, 4].
+    misses: rt_reproject_misses_host's no-variance form, the misses reprojected by direction."""
     L = lib or _lib.amd()
     arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (history, history_nd, history_ai, image, normal_depth, albedo_id)]
     img = arrs[3]
@@ -360,9 +361,15 @@ def reproject_host(history, history_nd, history_ai, history_camera, image, tile_
         tf = np.full(nt, tf[0], np.int32)
     out = np.empty_like(img)
     fp = lambda a: a.ctypes.data_as(c_float_p)  # noqa: E731
-    rc = L.rt_reproject_host(fp(arrs[0]), fp(arrs[1]), fp(arrs[2]), fp(cams[0]), fp(img),
-                             tf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(tf.size), fp(arrs[4]), fp(arrs[5]),
-                             fp(cams[1]), W, H, _reproject_params(cos_min, kz, max_history), fp(out))
+    if misses:
+        rc = L.rt_reproject_misses_host(fp(arrs[0]), fp(arrs[1]), fp(arrs[2]), None, fp(cams[0]), fp(img), None,
+                                        tf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(tf.size), fp(arrs[4]),
+                                        fp(arrs[5]), fp(cams[1]), W, H, _reproject_params(cos_min, kz, max_history), fp(out),
+                                        None)
+    else:
+        rc = L.rt_reproject_host(fp(arrs[0]), fp(arrs[1]), fp(arrs[2]), fp(cams[0]), fp(img),
+                                 tf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(tf.size), fp(arrs[4]), fp(arrs[5]),
+                                 fp(cams[1]), W, H, _reproject_params(cos_min, kz, max_history), fp(out))
     if rc != 0:
         raise RTError(rc, "rt_reproject_host: cos_min in [-1, 1], kz >= 0, max_history > 0, one count >= 0 per 8x8 tile "
                           "and a history camera with independent pixel deltas and view corner required")
@@ -397,9 +404,10 @@ def history_variance_host(image, m2, tile_frames, lib=None):
 
 
 def reproject_variance_host(history, history_nd, history_ai, history_s2, history_camera, image, m2, tile_frames, normal_depth,
-                            albedo_id, camera, cos_min=None, kz=None, max_history=None, lib=None):
+                            albedo_id, camera, cos_min=None, kz=None, max_history=None, lib=None, misses=False):
     """rt_reproject_variance_host (host only): reproject_host with the history's s2 [H, W] and the current
-    view's M2 [H, W, 4] -> ([H, W, 4] float32 (r, g, b, n_out), [H, W] float32 s2)."""
+    view's M2 [H, W, 4] -> ([H, W, 4] float32 (r, g, b, n_out), [H, W] float32 s2).
+    misses: rt_reproject_misses_host's variance form, the misses reprojected by direction."""
     L = lib or _lib.amd()
     arrs = [np.ascontiguousarray(a, dtype=np.float32) for a in (history, history_nd, history_ai, image, m2, normal_depth, albedo_id)]
     img = arrs[3]
@@ -415,9 +423,10 @@ def reproject_variance_host(history, history_nd, history_ai, history_s2, history
     tf = _tile_frames_of(tile_frames, W, H)
     out, s2 = np.empty_like(img), np.empty((H, W), np.float32)
     fp = lambda a: a.ctypes.data_as(c_float_p)  # noqa: E731
-    rc = L.rt_reproject_variance_host(fp(arrs[0]), fp(arrs[1]), fp(arrs[2]), fp(hs2), fp(cams[0]), fp(img), fp(arrs[4]),
-                                      tf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(tf.size), fp(arrs[5]), fp(arrs[6]),
-                                      fp(cams[1]), W, H, _reproject_params(cos_min, kz, max_history), fp(out), fp(s2))
+    entry = L.rt_reproject_misses_host if misses else L.rt_reproject_variance_host
+    rc = entry(fp(arrs[0]), fp(arrs[1]), fp(arrs[2]), fp(hs2), fp(cams[0]), fp(img), fp(arrs[4]),
+               tf.ctypes.data_as(ctypes.POINTER(ctypes.c_int32)), int(tf.size), fp(arrs[5]), fp(arrs[6]),
+               fp(cams[1]), W, H, _reproject_params(cos_min, kz, max_history), fp(out), fp(s2))
     if rc != 0:
         raise RTError(rc, "rt_reproject_variance_host: cos_min in [-1, 1], kz >= 0, max_history > 0, one count >= 0 per 8x8 "
                           "tile and a history camera with independent pixel deltas and view corner required")
@@ -833,6 +842,11 @@ class RenderContext:
         result (off by default; a change drops both)."""
         self._check(self._L.rt_set_history_variance(self._h, 1 if on else 0))
         self._history_variance = bool(on)
+
+    def set_reproject_misses(self, on=True):
+        """rt_set_reproject_misses: reproject() carries a miss (the background, seen through the scene's fog) over
+        by its ray's direction too.  Off by default; changing it drops the reprojected result and keeps the history."""
+        self._check(self._L.rt_set_reproject_misses(self._h, 1 if on else 0))
 
     def read_reprojected_variance(self):
         """rt_read_reprojected_variance: the result's s2 as [H, W] float32 (negative: unknown)."""
