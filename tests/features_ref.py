@@ -32,6 +32,7 @@ SPHERE, QUAD, MEDIUM, BOX = 1, 2, 3, 4
 MAT_DIFFUSE_LIGHT = 3
 TEX_IMAGE = 1
 INF = 3.402823e38   # RT_INFINITY
+_SCENE = rtamd.Scene   # the class, whatever a tool binds rtamd.Scene to later
 
 # (scene, W, H) of the GPU comparison, and the largest share of tied pixels the helper accepts per
 # scene (counted on the CPU at these sizes: 13 of 1024 on scenes 6 and 7 -- the Cornell box's edges, where
@@ -87,13 +88,39 @@ def _texture_colors(scene, tex_ids, p, uv):
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def reference(scene_id, W, H, seed=1):
-    """The expected buffers of scene `scene_id` at W x H, computed once per process:
+def _reference_once(scene, W=None, H=None, seed=1):
+    """reference() without the cache (reference.__wrapped__, as tools/reproject_quality.py calls it: a scene id
+    is built through rtamd.Scene as it is bound at the call)."""
+    if isinstance(scene, _SCENE):
+        assert (W is None or W == scene.width) and (H is None or H == scene.height)
+        return _reference(scene)
+    built = rtamd.Scene(int(scene), W, H, seed=seed)
+    try:
+        return _reference(built)
+    finally:
+        built.close()
+
+
+_reference_cached = functools.lru_cache(maxsize=None)(_reference_once)
+
+
+def reference(scene, W=None, H=None, seed=1):
+    """The expected buffers of a built-in scene (its id, at W x H; computed once per process) or of an
+    rtamd.Scene (at its own size, computed at every call; the scene stays the caller's):
     t [H, W] f32 (-1 on a miss), hit [H, W] bool, id [H, W] u32, ids_ok [H, W] list of the ids a tied
     pixel may hold, N [H, W, 3], A [H, W, 3], tied [H, W] bool, sign_free [H, W] bool (N up to its sign),
     a_free [H, W] bool (A not compared), background [3]."""
-    scene = rtamd.Scene(scene_id, W, H, seed=seed)
+    if isinstance(scene, _SCENE):
+        return _reference_once(scene, W, H)
+    return _reference_cached(scene, W, H, seed)
+
+
+reference.__wrapped__ = _reference_once
+reference.cache_clear = _reference_cached.cache_clear
+
+
+def _reference(scene):
+    W, H = scene.width, scene.height
     o, d = camera_rays(scene.camera, W, H)
     n_px = W * H
     dd = d.reshape(n_px, 3)
@@ -200,7 +227,6 @@ def reference(scene_id, W, H, seed=1):
     if tm.any():
         A[tm] = _texture_colors(scene, tex_id[tm], p[tm], tuv[tm])
     A[light] = np.where(front[light][:, None], emis[light], F(0.0))
-    scene.close()
     return types.SimpleNamespace(
         t=t.reshape(H, W), hit=hit.reshape(H, W), id=ids.reshape(H, W),
         ids_ok=[ids_ok[y * W:(y + 1) * W] for y in range(H)], N=N.reshape(H, W, 3), A=A.reshape(H, W, 3),

@@ -8,6 +8,9 @@ whose bottom row is 5 pixels high.  tests/test_kernel_matrix.py keeps this table
 tests/test_gpu_kernel_matrix.py launches every entry and compares its image with the CPU oracle.
 
 DEAD are the four instances no rt_render call can launch (tests/test_kernel_matrix.py says why).
+
+planned() and launch() are the launch check the GPU files share (tests/test_gpu_random_scenes.py too): what the
+host plans for a launch, and one rt_render held to that plan field by field.
 """
 import functools
 
@@ -105,13 +108,15 @@ def kernels():
     return [(b, o | m) for m in (0, MASKED) for b, o in ROWS]
 
 
-def planned(scene, frames, first_frame, options, mask, prev, waves, free_bytes, spp=FRAMES):
+def planned(scene, frames, first_frame, options, mask, prev, waves, free_bytes, spp=FRAMES, partition=None):
     """What rt_render would launch (tests/test_gpu_scene_plan.py predicted, with the kernel): the whole
-    rt_debug_last_launch as a list, the first-leaf words, the tile counts after, and (block, opt)."""
+    rt_debug_last_launch as a list, the first-leaf words, the tile counts after, and (block, opt).
+    partition: (rank, world, stripe_rows) of a stripe-partitioned context."""
     prev = np.asarray(prev, np.int32)
     uniform = len(set(prev.tolist())) == 1
+    part = {} if partition is None else dict(zip(("rank", "world", "stripe_rows"), partition))
     got = rtamd.plan_scene(scene, frames, first_frame=first_frame, options=options, mask=mask, prev_frames=int(prev.min()),
-                           prev_tile_frames=None if uniform else prev, waves=waves, free_bytes=free_bytes, spp=spp)
+                           prev_tile_frames=None if uniform else prev, waves=waves, free_bytes=free_bytes, spp=spp, **part)
     assert got["launched"] == 1
     out, info = plan(got["pk"][None, :], [0])
     assert out[0][PKO["OK"]] == 1, (options, mask)
@@ -119,3 +124,33 @@ def planned(scene, frames, first_frame, options, mask, prev, waves, free_bytes, 
         info[0][LI[f]] = got[f]
     kernel = (int(out[0][PKO["BLOCK"]]), int(out[0][PKO["OPT"]]))
     return [int(x) for x in info[0]], [x & 0xFFFFFFFF for x in got["first_leaf"]], got["tile_frames"], kernel
+
+
+def launch(ctx, kernel, label, scene, options, mask, first, frames, waves, partition=None):
+    """One rt_render of `frames` frames from `first` on a device context (the GPU tests' step): planned on the
+    host first, from the device's free memory and `waves`, then all 21 reported fields, the first-leaf words and
+    the tile counts equal to the plan, whose kernel is `kernel` (None: whichever the plan names).  Returns the
+    planned (block, opt).  Under a partition (rt_read_tile_frames does not serve one) the counts are the frames
+    rendered so far, first - 1 in every tile of the stripe, and are not read back."""
+    import torch
+    if partition is None:
+        before = ctx.read_tile_frames()
+    else:
+        before = np.full(((ctx.width + 7) // 8) * ((ctx.local_rows + 7) // 8), first - 1, np.int32)
+    free_bytes = torch.cuda.mem_get_info(0)[0]
+    want_launch, want_leaf, want_frames, want_kernel = planned(scene, frames, first, options, mask, before, waves,
+                                                               free_bytes, partition=partition)
+    assert kernel is None or want_kernel == kernel, f"{label}: frame {first} plans {want_kernel}"
+    ctx.render(first, rtamd.frame_rand_factors(1, first - 1, frames))
+    ctx.sync()
+    ll, fl = ctx.last_launch(), ctx.first_leaf()
+    got_launch = [ll[n] for n in rtamd.render.LAUNCH_FIELDS]
+    print(want_kernel, label, "mask" if mask is not None else "full", first, got_launch)
+    assert len(got_launch) == 21 and got_launch == want_launch, \
+        (label, first, dict(zip(rtamd.render.LAUNCH_FIELDS, want_launch)), ll)
+    assert [fl["armed"], fl["link"], fl["types"], fl["prims"]] == want_leaf, (label, first, fl)
+    if partition is None:
+        assert np.array_equal(ctx.read_tile_frames(), want_frames), (label, first)
+    else:
+        assert (np.asarray(want_frames) == first - 1 + frames).all() and len(want_frames) == before.size, (label, first)
+    return want_kernel

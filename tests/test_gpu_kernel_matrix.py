@@ -108,23 +108,7 @@ def run(kernel, label, name, options, mask):
         ctx.close()
 
 
-def launch(ctx, kernel, label, scene, options, mask, first, frames, waves):
-    """One rt_render of `frames` frames from `first`: planned on the host first, then all 21 reported fields,
-    the first-leaf words and the tile counts equal to the plan, whose kernel is the test's id."""
-    before = ctx.read_tile_frames()
-    free_bytes = torch.cuda.mem_get_info(0)[0]
-    want_launch, want_leaf, want_frames, want_kernel = km.planned(scene, frames, first, options, mask, before, waves,
-                                                                  free_bytes)
-    assert want_kernel == kernel, f"{label}: frame {first} plans {want_kernel}"
-    ctx.render(first, rtamd.frame_rand_factors(1, first - 1, frames))
-    ctx.sync()
-    ll, fl = ctx.last_launch(), ctx.first_leaf()
-    got_launch = [ll[n] for n in rtamd.render.LAUNCH_FIELDS]
-    print(kernel, label, "mask" if mask is not None else "full", first, got_launch)
-    assert len(got_launch) == 21 and got_launch == want_launch, \
-        (label, first, dict(zip(rtamd.render.LAUNCH_FIELDS, want_launch)), ll)
-    assert [fl["armed"], fl["link"], fl["types"], fl["prims"]] == want_leaf, (label, first, fl)
-    assert np.array_equal(ctx.read_tile_frames(), want_frames), (label, first)
+launch = km.launch   # shared with tests/test_gpu_random_scenes.py
 
 
 @pytest.mark.parametrize("kernel", KERNELS, ids=[f"{b}-{o}" for b, o in KERNELS])
