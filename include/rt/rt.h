@@ -724,6 +724,103 @@ int rt_render_moved_refined(rt_ctx* ctx, const float camera[28], int n_frames, c
                             const rt_denoise_params* denoise, const rt_guide_params* guides,
                             const rt_present_params* present, int* tiles_refined);
 
+/* ---- After a move: render until the moved view meets a noise target, tile by tile -----------------------
+ * The count criterion above sends frames to every fresh pixel alike.  With rt_set_history_variance(ctx, 1) the
+ * reprojected result carries a per-sample variance s2 of y, so the variance of a pixel's mean, s2 / n_out, is
+ * known wherever two or more samples stand behind the pixel.  rt_noise_tiles reduces it to one record per 8x8
+ * tile on the device, rt_refine_noise_select applies rt_adaptive_select's rule to the records on the host, and
+ * rt_render_moved_to_noise renders masked batches until every tile meets the target or a round cap, reading
+ * back 16 bytes per tile and round.  The records are a buffer of their own (allocated by the first
+ * rt_noise_tiles; a context that never calls these allocates and runs nothing new): image, moments, counts,
+ * features, history, the reprojected result and its s2, the denoised buffer, the presented frame and the reach
+ * records keep their bits.  Single-device contexts without rt_set_partition (RT_ERR_STATE).
+ *
+ * The record.  One per 8x8 tile of the image, tiles row-major, ceil(W/8) per row (the tiles of
+ * rt_read_tile_sums), made from the held rt_reproject result R = (r, g, b, n), its variance word s2
+ * (rt_read_reprojected_variance's) and a threshold min_count.  All arithmetic is f32 without contraction, using
+ * only +, /, comparisons and fabsf, so a float32 restatement matches bit for bit.  Lane ty*8+tx holds the pixel
+ * (tile_x*8+tx, tile_y*8+ty); `in` is true when that pixel lies in the image; finite(x) is fabsf(x) <= FLT_MAX.
+ *   y     = (R.r + R.g) + R.b;
+ *   good  = in && finite(y) && n > 0 && finite(n)     (the complement of rt_denoise_reprojected's "bad", plus a
+ *                                                      finite count);
+ *   known = good && s2 >= 0 && finite(s2)             (rt_reproject writes -1 where no variance is known);
+ *   thin  = good && (!known || !(n >= min_count));
+ *   v     = known ? s2 / n : +0                       (the variance of the pixel's mean);
+ *   yv    = good ? y : +0;
+ *   for off = 32, 16, 8, 4, 2, 1 (every lane at once, x[lane ^ off] its partner's value before the step):
+ *     v = v + v[lane ^ off];   yv = yv + yv[lane ^ off];
+ *   v_sum = lane 0's v;   y_sum = lane 0's yv;
+ *   known_px = the number of known lanes;   thin_px = the number of thin lanes;
+ *   bad_px = the number of lanes with in && !good;   pixels = the number of lanes that are in.
+ * csrc/rt_refine_math.h holds these operations once, for the kernel and for rt_tile_noise_host. */
+typedef struct rt_tile_noise { float v_sum, y_sum; uint16_t known_px, thin_px, bad_px, pixels; } rt_tile_noise; /* 16 bytes */
+/* rt_refine_noise_select's figures over all tiles, and rt_render_moved_to_noise's rounds and outcome. */
+typedef struct rt_moved_noise_stats { double sum_v, sum_y; uint64_t known, thin, bad, pixels; int rounds, converged; double noise; } rt_moved_noise_stats;
+/* target_noise >= 0 and finite.  min_count: 0 = automatic, 2, the fewest frames from which the moments give an
+ * estimate; otherwise > 0 and finite.  batch_frames >= 1: the frames an active tile gets per round.
+ * max_rounds >= 0: the cap (0: a noise figure and no extra frames).  reserved 0.  RT_ERR_INVALID_ARG otherwise. */
+typedef struct rt_noise_refine_params { float target_noise, min_count; int batch_frames, max_rounds; int reserved[4]; /* must be 0 */ } rt_noise_refine_params;
+
+/* Queue the kernel on the context's stream behind what is queued.  The record buffer is n_tiles * 16 bytes,
+ * allocated by the first call.  RT_ERR_INVALID_ARG unless min_count > 0 and finite.  RT_ERR_STATE naming what
+ * is lacking: no reprojected result held (rt_reproject first), a result without variance
+ * (rt_set_history_variance(ctx, 1) first), a multi-device context, one under rt_set_partition, no image.  The
+ * records belong to the result they were made from: they are held until the next rt_noise_tiles, rt_reproject,
+ * rt_resize or rt_destroy, or until rt_set_reproject_misses or rt_set_history_variance change value.  Reach
+ * records and noise records are held side by side. */
+int rt_noise_tiles(rt_ctx* ctx, float min_count);
+/* rt_sync, then the records.  out may be NULL to query *n_tiles; RT_ERR_LIMIT if cap is short;
+ * RT_ERR_STATE with no records held. */
+int rt_read_tile_noise(rt_ctx* ctx, rt_tile_noise* out, int cap, int* n_tiles);
+/* Host only, no device: the same header's arithmetic over caller arrays.  rgbn: W*H*4 floats (r, g, b, n), as
+ * rt_read_reprojected gives them; s2: W*H floats, as rt_read_reprojected_variance gives them;
+ * n_tiles = ceil(W/8) * ceil(H/8) and min_count > 0 and finite (RT_ERR_INVALID_ARG otherwise). */
+int rt_tile_noise_host(const float* rgbn, const float* s2, int width, int height, float min_count, rt_tile_noise* out,
+                       int n_tiles);
+/* Host only, pure; rt_adaptive_select's rule over the noise records.  In double, tiles in index order, with
+ * G_t = pixels_t - bad_px_t (the good pixels) and K_t = known_px_t:
+ *   ybar = sum_t y_sum_t / sum_t G_t over ALL tiles (0 when no pixel is good);
+ *   lim  = (double)target * ybar;
+ *   v_t  = (double)v_sum_t / K_t;
+ * a tile is active when active_in[t] is set (active_in NULL: all are), G_t > 0, and thin_px_t >= 1 or
+ * (K_t > 0 and v_t > lim * lim).  An inactive tile stays inactive.  Thin pixels force activity for the reason
+ * rt_adaptive_select has min_frames: a dark pixel whose samples are all zero so far has a variance estimate of
+ * 0, which passes any limit, and a 1-frame fresh pixel has no estimate at all -- neither may stop its tile.
+ * stats (may be NULL), with K = sum_t K_t: sum_v, sum_y, known, thin, bad, pixels are the plain sums over all
+ * tiles; noise = sqrt(sum_v / K) / ybar, 0 when sum_v is 0 and K > 0, +inf when K is 0 or ybar alone is 0;
+ * rounds and converged are left 0.  target >= 0 and finite.  RT_ERR_INVALID_ARG otherwise, and for NULL tiles
+ * or active_out with n_tiles > 0, any count over 64, known_px + bad_px > pixels.  n_active may be NULL. */
+int rt_refine_noise_select(const rt_tile_noise* tiles, const uint8_t* active_in, int n_tiles, float target,
+                           uint8_t* active_out, int* n_active, rt_moved_noise_stats* stats);
+/* rt_render_moved, then masked batches until every tile meets target_noise or max_rounds is reached.  With
+ * refine NULL it is rt_render_moved exactly.  Otherwise it is this sequence of the public calls and nothing
+ * else, each step's refusal returned unchanged:
+ *   rt_render_moved's steps 1 - 5 (capture, camera, rt_render(1, n_frames, rand_factors), features, reproject);
+ *   active = all tiles, r = 0, then:
+ *   a. rt_noise_tiles(mc), mc = refine->min_count if that is > 0, else 2;
+ *   b. rt_read_tile_noise -- the round's one rt_sync;
+ *   c. rt_refine_noise_select(records, active, target_noise) -> active, n_active, stats;
+ *   d. n_active == 0: converged = 1, stop;   r == max_rounds: converged = 0, stop;
+ *   e. rt_set_active_tiles(mask) (NULL when every tile is active),
+ *      rt_render(n_frames + r * batch_frames + 1, batch_frames, rand_factors + n_frames + r * batch_frames),
+ *      rt_set_active_tiles(NULL, 0), rt_reproject(reproject) again over the same history;  r = r + 1;  back to a;
+ *   rt_render_moved's steps 6 and 7 (rt_denoise_reprojected, rt_present), over the last result.
+ * The active set only shrinks, so every active tile holds n_frames + r * batch_frames frames and each masked
+ * launch continues its tiles' counts.  A tile that stopped after j rounds holds, in image and moments, the bits
+ * of a plain (n_frames + j * batch_frames)-frame render, and its count says so: the tiles end with different
+ * numbers of extra frames.  A pixel whose moments are not finite stays thin, so its tile runs to the round cap;
+ * the cap is what bounds that tile.  rand_factors holds n_frames + batch_frames * max_rounds values.
+ * Outputs (each may be NULL): *rounds_done = r; *tiles_refined = the tiles rendered in the first round;
+ * *tile_frames_spent = the sum over the rounds of n_active * batch_frames; *last = the final stats, with rounds
+ * and converged filled.  RT_ERR_STATE if a caller mask is set on entry (as rt_render_adaptive) or
+ * rt_set_history_variance is off; no mask is left set, also when a step refuses.  RT_ERR_INVALID_ARG for bad
+ * refine params (rt_noise_refine_params above) and when n_frames + batch_frames * max_rounds overflows. */
+int rt_render_moved_to_noise(rt_ctx* ctx, const float camera[28], int n_frames, const float* rand_factors,
+                             const rt_noise_refine_params* refine, const rt_reproject_params* reproject,
+                             const rt_denoise_params* denoise, const rt_guide_params* guides,
+                             const rt_present_params* present, int* rounds_done, int* tiles_refined,
+                             int64_t* tile_frames_spent, rt_moved_noise_stats* last);
+
 /* Per-frame u_rand_factor for frame index f (0-based) of a seeded render:
  * top 24 bits of splitmix64(seed, f) / 2^24, in [0,1).  Stands in for the
  * reference's (float)Math.random() per frame (RaytraceExecutor.java:124). */

@@ -125,7 +125,7 @@ int rt_destroy(rt_ctx* c) {
         dev_free(d.ft_nd); dev_free(d.ft_ai); dev_free(d.ft_links); dev_free(d.ft_args);
         dev_free(d.hs_px); dev_free(d.hs_nd); dev_free(d.hs_ai); dev_free(d.rp_out); dev_free(d.rp_counts);
         dev_free(d.hs_s2); dev_free(d.rp_s2); dev_free(d.pr_out); dev_free(d.pr_float); dev_free(d.pr_lut);
-        dev_free(d.rf_tiles);
+        dev_free(d.rf_tiles); dev_free(d.nz_tiles);
         comm_destroy(d);
         if (d.ring) (void)hipHostFree(d.ring);
         for (auto& e : d.ring_ev)
@@ -239,7 +239,7 @@ int rt_resize(rt_ctx* c, int w, int h) {
     features_free(c);       // ... and so were the first-hit buffers
     reproject_free(c);      // ... the history and the reprojected result
     present_free(c);        // ... and the presented frame (a bound frame buffer was the old size's too)
-    refine_free(c);         // ... and the reach records
+    refine_free(c);         // ... and the reach and noise records
     set_all_frames(c, 0);   // another image: no tile holds a frame, and a tile mask no longer fits it
     c->mask_set = false;
     c->act_list.clear();

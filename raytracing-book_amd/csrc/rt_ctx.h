@@ -62,6 +62,7 @@ struct Device {
     void* pr_ptr = nullptr;  // ... the active frame buffer (internal or bound: rt_bind_device_present)
     bool pr_bound = false;
     DevBuf rf_tiles;         // rt_reach_tiles: one rt_tile_reach per 8x8 tile (rt_refine.hip)
+    DevBuf nz_tiles;         // rt_noise_tiles: one rt_tile_noise per 8x8 tile (rt_refine.hip)
     DevBuf wbuf;             // pooled units (ordered / one chunk): per resident wave 64 x chunk_frames colours
     DevBuf finfo;            // exact near-first walk tables (variant 61)
     DevBuf f2inner, f2leaves;
@@ -127,6 +128,8 @@ struct rt_ctx : rt_impl::SceneState {
     bool pr_valid = false, pr_float_valid = false;
     // rt_reach_tiles: the rp_gen of the result the reach records in Device::rf_tiles were made from, 0 when none are held
     uint32_t rf_rp_gen = 0;
+    // rt_noise_tiles: likewise for the noise records in Device::nz_tiles
+    uint32_t nz_rp_gen = 0;
     // the first device's staged colours of the last launch (rt_debug_read_samples): frames, sparse flags
     int staged_frames = 0;
     bool staged_sparse = false;

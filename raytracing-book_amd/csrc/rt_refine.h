@@ -10,8 +10,17 @@ struct rt_rf_resolved {
     int extra_frames, min_pixels, max_tiles;
 };
 
+// rt_noise_refine_params checked and resolved (min_count 0 = automatic, 2)
+struct rt_nz_resolved {
+    float target_noise, min_count;
+    int batch_frames, max_rounds;
+};
+
 namespace rt_impl __attribute__((visibility("hidden"))) {
 
+// RT_OK, or RT_ERR_INVALID_ARG: a target_noise or min_count that is negative or not finite, batch_frames < 1,
+// max_rounds < 0, reserved not 0
+int noise_refine_resolve(const rt_noise_refine_params* p, rt_nz_resolved* out);
 // RT_OK, or RT_ERR_INVALID_ARG: extra_frames < 0, min_pixels outside 0 .. 64, max_tiles < 0, a min_count that
 // is negative or not finite, reserved not 0
 int refine_resolve(const rt_refine_params* p, rt_rf_resolved* out);

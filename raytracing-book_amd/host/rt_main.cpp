@@ -50,6 +50,10 @@
 // (rt_render_moved_refined); --move-refine-count <C> names the count below which a pixel is short (default
 // N + K) and --move-refine-tiles <M> caps the tiles refined per pose.  Pose k then takes the factors of frame
 // indices spp + (k - 1) * (N + K) onwards, N for the pose and K for the refinement.
+// --move-noise <x> renders each pose until every 8x8 tile meets the relative noise x or a round cap
+// (rt_render_moved_to_noise): --move-noise-batch <B> frames per round (default 1), --move-noise-rounds <R> rounds at
+// most (default 4), --move-noise-count <C> the count below which a pixel is thin (default 2).  Pose k then takes the
+// factors of frame indices spp + (k - 1) * (N + B * R) onwards.  It does not combine with --move-refine.
 // --move-misses reprojects the pixels whose centre ray hits nothing by the ray's direction too
 // (rt_set_reproject_misses): the background keeps its history, and fewer tiles qualify for --move-refine.
 #include "rt/rt.h"
@@ -77,7 +81,7 @@ struct Opt {
 };
 
 // commons-cli Options in Main.getOptions order (Main.java:43-70)
-enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_DENOISE, O_DENOISE_LEVELS, O_DENOISE_K, O_RAW_OUT, O_DENOISE_GUIDES, O_DENOISE_KN, O_DENOISE_KZ, O_DENOISE_KA, O_FEATURES_OUT, O_MOVES, O_MOVE_SHIFT, O_MOVE_FRAMES, O_MOVE_REFINE, O_MOVE_REFINE_COUNT, O_MOVE_REFINE_TILES, O_MOVE_MISSES, O_N };
+enum { O_HELP, O_SCENE, O_RES, O_SPP, O_DEPTH, O_OUT, O_SEED, O_DEVICES, O_PER_LAUNCH, O_PREVIEW, O_PREVIEW_EVERY, O_NOISE, O_ADAPTIVE, O_MIN_FRAMES, O_DENOISE, O_DENOISE_LEVELS, O_DENOISE_K, O_RAW_OUT, O_DENOISE_GUIDES, O_DENOISE_KN, O_DENOISE_KZ, O_DENOISE_KA, O_FEATURES_OUT, O_MOVES, O_MOVE_SHIFT, O_MOVE_FRAMES, O_MOVE_REFINE, O_MOVE_REFINE_COUNT, O_MOVE_REFINE_TILES, O_MOVE_MISSES, O_MOVE_NOISE, O_MOVE_NOISE_BATCH, O_MOVE_NOISE_ROUNDS, O_MOVE_NOISE_COUNT, O_N };
 const Opt kOpts[O_N] = {
     {"h", "help", false, "print help message"},
     {"s", "scene", true, "scene ID"},
@@ -110,6 +114,10 @@ const Opt kOpts[O_N] = {
     {nullptr, "move-refine-count", true, "with --move-refine: a pixel is short below this count (default: the frames a refined tile gets)"},
     {nullptr, "move-refine-tiles", true, "with --move-refine: at most this many tiles refined per pose (default: no cap)"},
     {nullptr, "move-misses", false, "with --moves: reproject the background (pixels that hit nothing) by ray direction too"},
+    {nullptr, "move-noise", true, "with --moves: render each pose until every 8x8 tile meets this relative noise"},
+    {nullptr, "move-noise-batch", true, "with --move-noise: frames per round on the tiles still above the target (default 1)"},
+    {nullptr, "move-noise-rounds", true, "with --move-noise: rounds per pose at most (default 4)"},
+    {nullptr, "move-noise-count", true, "with --move-noise: a pixel is thin below this count (default 2)"},
 };
 
 // HelpFormatter.printHelp("OpenGL Ray Tracer", options): options sorted by key.
@@ -330,6 +338,14 @@ int main(int argc, char** argv) {
     if (!moving && seen[O_MOVE_MISSES]) die("rtrender", "--move-misses goes with --moves");
     if (!seen[O_MOVE_REFINE] && (seen[O_MOVE_REFINE_COUNT] || seen[O_MOVE_REFINE_TILES]))
         die("rtrender", "--move-refine-count and --move-refine-tiles go with --move-refine");
+    const bool noise_moves = seen[O_MOVE_NOISE];
+    int move_noise_batch = 1, move_noise_rounds = 4;
+    float move_noise = 0.0f, move_noise_count = 0.0f;
+    if (!moving && (noise_moves || seen[O_MOVE_NOISE_BATCH] || seen[O_MOVE_NOISE_ROUNDS] || seen[O_MOVE_NOISE_COUNT]))
+        die("rtrender", "--move-noise, --move-noise-batch, --move-noise-rounds and --move-noise-count go with --moves");
+    if (!noise_moves && (seen[O_MOVE_NOISE_BATCH] || seen[O_MOVE_NOISE_ROUNDS] || seen[O_MOVE_NOISE_COUNT]))
+        die("rtrender", "--move-noise-batch, --move-noise-rounds and --move-noise-count go with --move-noise");
+    if (noise_moves && seen[O_MOVE_REFINE]) die("rtrender", "--move-noise and --move-refine do not combine");
     if (moving) {
         if (!seen[O_MOVE_SHIFT] || !seen[O_MOVE_FRAMES])
             die("rtrender", "--moves needs --move-shift <S> and --move-frames <N>");
@@ -356,6 +372,22 @@ int main(int argc, char** argv) {
         if (seen[O_MOVE_REFINE_TILES]) {
             move_refine_tiles = parse_int(val[O_MOVE_REFINE_TILES]);
             if (move_refine_tiles < 1) die("rtrender", "--move-refine-tiles must be at least 1");
+        }
+        if (noise_moves) {
+            move_noise = std::strtof(val[O_MOVE_NOISE].c_str(), &end);
+            if (val[O_MOVE_NOISE].empty() || *end != '\0' || !(move_noise >= 0.0f) || !(move_noise <= 3.0e38f))
+                die("rtrender", "--move-noise must be a finite number >= 0");
+            if (seen[O_MOVE_NOISE_BATCH]) move_noise_batch = parse_int(val[O_MOVE_NOISE_BATCH]);
+            if (move_noise_batch < 1) die("rtrender", "--move-noise-batch must be at least 1");
+            if (seen[O_MOVE_NOISE_ROUNDS]) move_noise_rounds = parse_int(val[O_MOVE_NOISE_ROUNDS]);
+            if (move_noise_rounds < 0) die("rtrender", "--move-noise-rounds must be at least 0");
+            if ((long long)move_noise_batch * move_noise_rounds > (long long)INT_MAX - move_frames)
+                die("rtrender", "--move-noise-batch times --move-noise-rounds is too large");
+            if (seen[O_MOVE_NOISE_COUNT]) {
+                move_noise_count = std::strtof(val[O_MOVE_NOISE_COUNT].c_str(), &end);
+                if (val[O_MOVE_NOISE_COUNT].empty() || *end != '\0' || !(move_noise_count > 0.0f) || !(move_noise_count <= 3.0e38f))
+                    die("rtrender", "--move-noise-count must be a finite number > 0");
+            }
         }
     }
 
@@ -536,7 +568,8 @@ int main(int argc, char** argv) {
         const size_t dot = output.rfind('.');
         const bool has_ext = dot != std::string::npos && output.find('/', dot) == std::string::npos && dot > 0;
         const std::string stem = has_ext ? output.substr(0, dot) : output;
-        const int pose_frames = move_frames + move_refine;   // the pose's own, then the refinement's
+        // the pose's own, then the refinement's (--move-noise: every round's, rendered or not)
+        const int pose_frames = move_frames + (noise_moves ? move_noise_batch * move_noise_rounds : move_refine);
         std::vector<float> mrf((size_t)pose_frames);
         rt_refine_params refine;
         std::memset(&refine, 0, sizeof(refine));
@@ -544,7 +577,13 @@ int main(int argc, char** argv) {
         refine.extra_frames = move_refine;
         refine.max_tiles = move_refine_tiles;
         int n_tiles = 0;
-        if (move_refine) chk(rt_read_tile_frames(ctx, nullptr, 0, &n_tiles), "rt_read_tile_frames");
+        if (move_refine || noise_moves) chk(rt_read_tile_frames(ctx, nullptr, 0, &n_tiles), "rt_read_tile_frames");
+        rt_noise_refine_params to_noise;
+        std::memset(&to_noise, 0, sizeof(to_noise));
+        to_noise.target_noise = move_noise;
+        to_noise.min_count = move_noise_count;
+        to_noise.batch_frames = move_noise_batch;
+        to_noise.max_rounds = move_noise_rounds;
         std::vector<uint8_t> rgba8(n * 4), rgb8(n * 3);
         const float step = (float)((double)move_shift * width);
         for (int k = 1; k <= moves; k++) {
@@ -555,8 +594,15 @@ int main(int argc, char** argv) {
             }
             for (int i = 0; i < pose_frames; i++)
                 mrf[(size_t)i] = rt_frame_rand_factor((uint64_t)seed, (uint64_t)spp + (uint64_t)(k - 1) * pose_frames + i);
-            int refined = 0;
-            if (move_refine)
+            int refined = 0, rounds = 0;
+            int64_t spent = 0;
+            rt_moved_noise_stats mstats;
+            std::memset(&mstats, 0, sizeof(mstats));
+            if (noise_moves)
+                chk(rt_render_moved_to_noise(ctx, ubo, move_frames, mrf.data(), &to_noise, nullptr, nullptr, nullptr, nullptr, &rounds,
+                                             &refined, &spent, &mstats),
+                    "rt_render_moved_to_noise");
+            else if (move_refine)
                 chk(rt_render_moved_refined(ctx, ubo, move_frames, mrf.data(), &refine, nullptr, nullptr, nullptr, nullptr, &refined),
                     "rt_render_moved_refined");
             else
@@ -571,7 +617,11 @@ int main(int argc, char** argv) {
                 uncaught("java.lang.RuntimeException", "Failed to save texture as PNG");
             char abs_path[PATH_MAX];
             const char* shown = realpath(name.c_str(), abs_path) ? abs_path : name.c_str();
-            if (move_refine)
+            if (noise_moves)
+                std::printf("Move %d/%d: %d frame(s), +%lld tile-frame(s) in %d round(s) on %d of %d tiles, noise %.6g (%s), saved to: %s\n",
+                            k, moves, move_frames, (long long)spent, rounds, refined, n_tiles, mstats.noise,
+                            mstats.converged ? "converged" : "round cap reached", shown);
+            else if (move_refine)
                 std::printf("Move %d/%d: %d frame(s), +%d on %d of %d tiles, saved to: %s\n", k, moves, move_frames, move_refine,
                             refined, n_tiles, shown);
             else

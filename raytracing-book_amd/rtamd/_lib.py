@@ -113,6 +113,28 @@ class RtRefineParams(ctypes.Structure):
                 ("max_tiles", ctypes.c_int), ("reserved", ctypes.c_int * 4)]
 
 
+class RtTileNoise(ctypes.Structure):
+    """rt.h rt_tile_noise (numpy: TILE_NOISE_DTYPE)."""
+    _fields_ = [("v_sum", ctypes.c_float), ("y_sum", ctypes.c_float), ("known_px", ctypes.c_uint16),
+                ("thin_px", ctypes.c_uint16), ("bad_px", ctypes.c_uint16), ("pixels", ctypes.c_uint16)]
+
+
+class RtMovedNoiseStats(ctypes.Structure):
+    """rt.h rt_moved_noise_stats."""
+    _fields_ = [("sum_v", ctypes.c_double), ("sum_y", ctypes.c_double), ("known", ctypes.c_uint64),
+                ("thin", ctypes.c_uint64), ("bad", ctypes.c_uint64), ("pixels", ctypes.c_uint64),
+                ("rounds", ctypes.c_int), ("converged", ctypes.c_int), ("noise", ctypes.c_double)]
+
+    def as_dict(self):
+        return {n: getattr(self, n) for n, _ in self._fields_}
+
+
+class RtNoiseRefineParams(ctypes.Structure):
+    """rt.h rt_noise_refine_params."""
+    _fields_ = [("target_noise", ctypes.c_float), ("min_count", ctypes.c_float), ("batch_frames", ctypes.c_int),
+                ("max_rounds", ctypes.c_int), ("reserved", ctypes.c_int * 4)]
+
+
 RT_FEATURE_MISS = 0xFFFFFFFF   # rt.h
 
 RT_PK_N = 33   # rt_debug.h RT_PK_N
@@ -217,6 +239,17 @@ def _amd_protos(L, old_rev=False):
         _proto(L, "rt_set_reproject_misses", i, vp, i)
         _proto(L, "rt_reproject_misses_host", i, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p, c_float_p,
                i32_p, i, c_float_p, c_float_p, c_float_p, i, i, rp_p, c_float_p, c_float_p)
+    if not old_rev or hasattr(L, "rt_noise_tiles"):   # ... or from before the noise records
+        dp_p, gp_p = ctypes.POINTER(RtDenoiseParams), ctypes.POINTER(RtGuideParams)
+        rp_p, pp_p = ctypes.POINTER(RtReprojectParams), ctypes.POINTER(RtPresentParams)
+        tn_p, nr_p, u8_p = ctypes.POINTER(RtTileNoise), ctypes.POINTER(RtNoiseRefineParams), ctypes.POINTER(ctypes.c_uint8)
+        ms_p = ctypes.POINTER(RtMovedNoiseStats)
+        _proto(L, "rt_noise_tiles", i, vp, f)
+        _proto(L, "rt_read_tile_noise", i, vp, tn_p, i, c_int_p)
+        _proto(L, "rt_tile_noise_host", i, c_float_p, c_float_p, i, i, f, tn_p, i)
+        _proto(L, "rt_refine_noise_select", i, tn_p, u8_p, i, f, u8_p, c_int_p, ms_p)
+        _proto(L, "rt_render_moved_to_noise", i, vp, c_float_p, i, c_float_p, nr_p, rp_p, dp_p, gp_p, pp_p, c_int_p, c_int_p,
+               ctypes.POINTER(ctypes.c_int64), ms_p)
     _proto(L, "rt_abi_version", i)
     _proto(L, "rt_create", i, i, c_int_p, ctypes.POINTER(vp))
     _proto(L, "rt_destroy", i, vp)

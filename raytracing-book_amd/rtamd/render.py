@@ -545,6 +545,68 @@ def _refine_params(refine):
     return p
 
 
+TILE_NOISE_DTYPE = np.dtype([("v_sum", "<f4"), ("y_sum", "<f4"), ("known_px", "<u2"), ("thin_px", "<u2"),
+                             ("bad_px", "<u2"), ("pixels", "<u2")])   # rt.h rt_tile_noise
+
+
+def tile_noise_host(rgbn, s2, min_count, lib=None):
+    """rt_tile_noise_host (host only, no device): one TILE_NOISE_DTYPE record per 8x8 tile (row-major) of a
+    reprojected result [H, W, 4] float32 (r, g, b, n) and its s2 [H, W]: the summed variance of the pixels' means
+    and the summed y, the pixels whose variance is known, the thin ones (no variance, or a count below min_count),
+    the bad ones, the pixels in the image."""
+    L = lib or _lib.amd()
+    r = np.ascontiguousarray(rgbn, dtype=np.float32)
+    if r.ndim != 3 or r.shape[2] != 4:
+        raise ValueError("rgbn is [H, W, 4]")
+    v = np.ascontiguousarray(s2, dtype=np.float32)
+    if v.shape != r.shape[:2]:
+        raise ValueError("s2 is [H, W]")
+    H, W = r.shape[:2]
+    out = np.zeros(((W + 7) // 8) * ((H + 7) // 8), dtype=TILE_NOISE_DTYPE)
+    rc = L.rt_tile_noise_host(r.ctypes.data_as(c_float_p), v.ctypes.data_as(c_float_p), W, H, float(min_count),
+                              out.ctypes.data_as(ctypes.POINTER(_lib.RtTileNoise)), int(out.size))
+    if rc != 0:
+        raise RTError(rc, "rt_tile_noise_host: min_count > 0 and finite required")
+    return out
+
+
+def refine_noise_select(tiles, target, active=None, lib=None):
+    """rt_refine_noise_select (host only, pure): the tiles still active at the noise target -> (uint8 array, one per
+    tile; the stats as a dict).  A tile stays active while it has a thin pixel or its mean variance of the mean
+    exceeds (target * ybar)^2; active: the tiles active so far (None: all), an inactive tile stays inactive."""
+    L = lib or _lib.amd()
+    t = np.ascontiguousarray(tiles, dtype=TILE_NOISE_DTYPE)
+    a = None
+    if active is not None:
+        a = np.ascontiguousarray(active, dtype=np.uint8).ravel()
+        if a.size != t.size:
+            raise ValueError("active holds one byte per tile")
+    out = np.zeros(t.size, np.uint8)
+    n = ctypes.c_int()
+    stats = _lib.RtMovedNoiseStats()
+    u8_p = ctypes.POINTER(ctypes.c_uint8)
+    rc = L.rt_refine_noise_select(t.ctypes.data_as(ctypes.POINTER(_lib.RtTileNoise)), None if a is None else a.ctypes.data_as(u8_p),
+                                  int(t.size), float(target), out.ctypes.data_as(u8_p), ctypes.byref(n), ctypes.byref(stats))
+    if rc != 0:
+        raise RTError(rc, "rt_refine_noise_select: target >= 0 and finite, every count <= 64, known_px + bad_px <= pixels required")
+    return out, stats.as_dict()
+
+
+def _noise_refine_params(noise_refine):
+    """rt_noise_refine_params for a dict of target_noise and optionally batch_frames (1), max_rounds (4), min_count (0)."""
+    unknown = set(noise_refine) - {"target_noise", "batch_frames", "max_rounds", "min_count"}
+    if unknown:
+        raise ValueError(f"noise_refine: unknown keys {sorted(unknown)}")
+    if "target_noise" not in noise_refine:
+        raise ValueError("noise_refine: target_noise is required")
+    p = _lib.RtNoiseRefineParams()
+    p.target_noise = float(noise_refine["target_noise"])
+    p.min_count = float(noise_refine.get("min_count") or 0.0)
+    p.batch_frames = int(noise_refine.get("batch_frames", 1))
+    p.max_rounds = int(noise_refine.get("max_rounds", 4))
+    return p
+
+
 SHAPES = {0: "fast-lds", 1: "fast-global", 2: "link-lds", 3: "meta-lds", 4: "meta-global", 5: "link-two-level"}
 
 
@@ -906,15 +968,36 @@ class RenderContext:
                                                ctypes.byref(n)))
         return out
 
+    # -- the moved view rendered to a noise target (rt.h rt_noise_tiles / rt_render_moved_to_noise)
+    def noise_tiles(self, min_count=2.0):
+        """rt_noise_tiles: queue the reduction of the held reproject() result and its s2 to one noise record per
+        8x8 tile; a good pixel is thin when its variance is unknown or its count is below min_count."""
+        self._check(self._L.rt_noise_tiles(self._h, float(min_count)))
+
+    def read_tile_noise(self):
+        """rt_read_tile_noise: one TILE_NOISE_DTYPE record per 8x8 tile, row-major."""
+        n = ctypes.c_int()
+        self._check(self._L.rt_read_tile_noise(self._h, None, 0, ctypes.byref(n)))
+        out = np.zeros(n.value, dtype=TILE_NOISE_DTYPE)
+        self._check(self._L.rt_read_tile_noise(self._h, out.ctypes.data_as(ctypes.POINTER(_lib.RtTileNoise)), n.value,
+                                               ctypes.byref(n)))
+        return out
+
     def render_moved(self, camera, rand_factors, source=None, exposure=1.0, keep_float=False, cos_min=None, kz=None,
-                     max_history=None, levels=None, k=None, guides=True, refine=None):
+                     max_history=None, levels=None, k=None, guides=True, refine=None, noise_refine=None):
         """rt_render_moved + rt_read_presented: one pose of a moving camera -> [H, W, 4] uint8.  Captures the
         history, moves to `camera` (28 floats), renders len(rand_factors) frames from frame 1 and the features,
         reprojects, filters (under set_history_variance()) and presents.  source None: the library's choice
         ("moved" under set_history_variance(), else "reprojected") unless exposure or keep_float ask for
         parameters, then the same choice made here.  The other arguments are reproject()'s and denoise_reprojected()'s.
         refine: a dict of extra_frames and optionally min_count, min_pixels, max_tiles = rt_render_moved_refined ->
-        (frame, tiles refined): the last extra_frames of rand_factors go to the tiles the history does not reach."""
+        (frame, tiles refined): the last extra_frames of rand_factors go to the tiles the history does not reach.
+        noise_refine: a dict of target_noise and optionally batch_frames (1), max_rounds (4), min_count (0: automatic)
+        = rt_render_moved_to_noise -> (frame, info): the last batch_frames * max_rounds of rand_factors go, round by
+        round, to the tiles that have not met the target; info holds rounds_done, tiles_refined, tile_frames_spent
+        and the final stats (sum_v, sum_y, known, thin, bad, pixels, rounds, converged, noise)."""
+        if refine is not None and noise_refine is not None:
+            raise ValueError("refine and noise_refine do not combine")
         cam = np.ascontiguousarray(camera, dtype=np.float32).ravel()
         assert cam.size == 28
         rf = np.ascontiguousarray(rand_factors, dtype=np.float32)
@@ -924,6 +1007,20 @@ class RenderContext:
             src = source if source is not None else ("moved" if getattr(self, "_history_variance", False) else "reprojected")
             pp = _present_params(src, exposure, keep_float)
         g = (0.0, 0.0, 0.0) if guides is None or guides is False else guides
+        if noise_refine is not None:
+            nr = _noise_refine_params(noise_refine)
+            n = int(rf.size) - max(nr.batch_frames, 0) * max(nr.max_rounds, 0)
+            if n < 1:
+                raise ValueError("rand_factors holds the pose's frames and then batch_frames * max_rounds more")
+            rounds, tiles, spent, stats = ctypes.c_int(), ctypes.c_int(), ctypes.c_int64(), _lib.RtMovedNoiseStats()
+            self._check(self._L.rt_render_moved_to_noise(self._h, cam.ctypes.data_as(c_float_p), n, rf.ctypes.data_as(c_float_p),
+                                                         ctypes.byref(nr), _reproject_params(cos_min, kz, max_history),
+                                                         _denoise_params(levels, k), _guide_params(g), pp,
+                                                         ctypes.byref(rounds), ctypes.byref(tiles), ctypes.byref(spent),
+                                                         ctypes.byref(stats)))
+            info = dict(rounds_done=rounds.value, tiles_refined=tiles.value, tile_frames_spent=spent.value)
+            info.update(stats.as_dict())
+            return self.read_presented(), info
         if refine is not None:
             rp = _refine_params(refine)
             n = int(rf.size) - max(rp.extra_frames, 0)
